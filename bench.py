@@ -15,6 +15,14 @@ data-parallel part of the WorkStealing leg -- the per-task thief rows -- is shar
 the ranks and all-gathered.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--tasks N] [--workers W]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line: the headline
+figure and what the timed steps' own HIP events give (per-kernel times, the roofline).
+Everything that takes runs of its own (the CPU baselines and parity checks, the measured
+copy peak, the link latency and latency bound, the WorkStealing, C3, variant, service and
+C5 legs) is behind ``--full``, where the ``--no-*`` options still pick among them.
+``--dump-outputs DIR`` writes the placement log of the last timed step as DIR/<column>.npy.
 """
 from __future__ import annotations
 
@@ -49,6 +57,48 @@ def algorithmic_bytes(g: dict, placed_tasks: np.ndarray, n_waves: int) -> float:
     f = np.bincount(g["dep_idx"], minlength=n).astype(np.int64)[placed_tasks]
     per_task = 8 + 12 * k + 8 * k * WB + 12 + 8 + 12 * f
     return float(per_task.sum() + 48 * W * n_waves)
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(d: str, out: dict) -> None:
+    """The placement log a caller of the timed path receives (PlacementEngine.placements():
+    one row per placement, in placement order) as d/<column>.npy in float64, which holds
+    every column exactly (the int64 ones are byte counts far below 2^53). A log too large
+    for DUMP_BYTES is cut to a fixed, seeded sample of its rows, the same rows of every column."""
+    os.makedirs(d, exist_ok=True)
+    n = len(next(iter(out.values())))
+    rows = (DUMP_BYTES - 4096 * len(out)) // (8 * len(out))  # .npy headers set aside
+    idx = np.sort(np.random.default_rng(0).choice(n, rows, replace=False)) if n > rows else slice(None)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v[idx].astype(np.float64))
+
+
+def copy_peak_gbs(local: int):
+    """A measured copy peak beside the 8 TB/s datasheet figure: a 2 GiB
+    device-to-device copy, read + written bytes over its event-timed duration (best of 5)."""
+    try:
+        import torch
+
+        src = torch.empty(1 << 31, dtype=torch.uint8, device=f"cuda:{local}")
+        dst = torch.empty_like(src)
+        dst.copy_(src)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        best = None
+        for _ in range(5):
+            e0.record()
+            dst.copy_(src)
+            e1.record()
+            torch.cuda.synchronize()
+            ms_c = e0.elapsed_time(e1)
+            best = ms_c if best is None else min(best, ms_c)
+        gbs = round(2 * src.numel() / (best * 1e-3) / 1e9, 1)
+        del src, dst
+        torch.cuda.empty_cache()
+        return gbs
+    except Exception as ex:  # reported, never fatal
+        return f"unavailable: {ex}"
 
 
 def reduce_max(x: float, dist, device: str = "cuda") -> float:
@@ -584,7 +634,18 @@ def main():
     ap.add_argument("--c5-cpu-map", type=int, default=200_000, help="map tasks of the C5 CPU-baseline sample")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"))
     ap.add_argument("--no-latency", action="store_true", help="skip the link-latency chain and the latency bound")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: CPU baselines and parity, the copy peak, "
+                         "the latency bound and the steal / C3 / variant / service / C5 legs (the --no-* options "
+                         "pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the placement log of the last timed step as DIR/<column>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the timed steps and nothing that takes a run of its own
+        args.no_cpu_baseline = args.no_steal = args.no_c3 = args.no_c5 = True
+        args.no_service = args.no_variants = args.no_latency = True
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -644,6 +705,8 @@ def main():
     value = total_placements / elapsed
 
     out = eng.placements()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     agree = None
     if dist is not None and not args.no_cpu_baseline:
         # every rank checks its own replay against the oracle (its own graph); all must agree
@@ -707,28 +770,8 @@ def main():
             else:
                 result["roofline"]["traffic"] = round(t["traffic_bytes_per_launch"], 1)
                 result["roofline"]["traffic_source"] = t.get("source")
-        # a measured copy peak beside the 8 TB/s datasheet figure: a 2 GiB
-        # device-to-device copy, read + written bytes over its event-timed duration
-        try:
-            import torch
-
-            src = torch.empty(1 << 31, dtype=torch.uint8, device=f"cuda:{local}")
-            dst = torch.empty_like(src)
-            dst.copy_(src)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            best = None
-            for _ in range(5):
-                e0.record()
-                dst.copy_(src)
-                e1.record()
-                torch.cuda.synchronize()
-                ms_c = e0.elapsed_time(e1)
-                best = ms_c if best is None else min(best, ms_c)
-            result["roofline"]["copy_peak_measured"] = round(2 * src.numel() / (best * 1e-3) / 1e9, 1)
-            del src, dst
-            torch.cuda.empty_cache()
-        except Exception as ex:  # reported, never fatal
-            result["roofline"]["copy_peak_measured"] = f"unavailable: {ex}"
+        if args.full:
+            result["roofline"]["copy_peak_measured"] = copy_peak_gbs(local)
         if not args.no_latency:
             link_us = link_latency_us(PlacementEngine, local)
             result["latency_bound"] = latency_bound(g, out, link_us, 1e3 * elapsed / args.steps)

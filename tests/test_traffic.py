@@ -11,10 +11,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_hbm_traffic_matches_committed_counters(tmp_path):
     pinned = json.load(open(os.path.join(REPO, "profiles", "hbm_traffic.json")))
-    src = pinned["source"].split()[0]  # the profile directory holding the two passes
+    # the two passes behind the pinned file (pinned["source"] names the output folder of the
+    # session that measured them, which was never committed; tests/golden/pmc_r06p/README.md)
+    src = os.path.join(REPO, "tests", "golden", "pmc_r06p")
     out = tmp_path / "t.json"
-    subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "pmc_traffic.py"), os.path.join(REPO, src),
-                           str(out)], stdout=subprocess.DEVNULL)
+    subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "pmc_traffic.py"), src, str(out)],
+                          stdout=subprocess.DEVNULL)
     got = json.load(open(out))
     assert got["launches"] == {"FETCH_SIZE": 1, "WRITE_SIZE": 1}  # the C2 replay dispatch only
     assert got["traffic_bytes_per_launch"] == (2 * got["fetch_size_kib_per_launch"] + got["write_size_kib_per_launch"]) * 1024

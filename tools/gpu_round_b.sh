@@ -8,7 +8,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 echo "== rocprof"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --no-cpu-baseline --steps 2 --warmup 1 > $OUT/prof.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --full --no-cpu-baseline --steps 2 --warmup 1 > $OUT/prof.log 2>&1
 rc=$?; tail -2 $OUT/prof.log | cut -c1-300; [ $rc -ne 0 ] && exit $rc
 for C in FETCH_SIZE WRITE_SIZE; do
   echo "== pmc $C"
