@@ -1260,10 +1260,13 @@ __device__ void exec_local_wave(const Dev& D, int j, int t, int w, unsigned long
     }
     if (ovf) {
       // scan mode for c: publish the processing_on of this stimulus' earlier placements
-      // first (the scan reads them), then decide each dependency exactly
+      // first (the scan reads them) and that t no longer processes on w (c may be w: a
+      // dependency t shared with x is not needed by t any more), then decide each
+      // dependency exactly
       if (lane == NEEDS_W - 1) e = NEEDS_OVF;
       dirty = true;
       if (xw >= 0) D.proc_on[xl] = xw;
+      if (lane == 0) D.proc_on[t] = -1;
       __threadfence_block();
       const int64_t mine = (dxl >= 0 && !hx && !needed_elsewhere(D, dxl, c, x)) ? nbx : 0;
       dnx = wave_sum64(mine);

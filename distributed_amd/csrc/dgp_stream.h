@@ -2708,6 +2708,10 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
     o.place(D, x, cb, best.comm, best.start, best.nb, ROUTE_NONROOTISH);
     uint32_t nlc = line_load<LW>(P, cb);
     if (exact) {  // scan mode reads processing_on of this stimulus' earlier placements
+      // ... and of t, which left w above: a dependency t shares with x, placed on w, is not
+      // needed by t any more (only an exact stimulus, the oldest, scans; the sequencer
+      // writes this again at retirement)
+      if (lane == 0) D.proc_on[rl((int)E.x, 0)] = -1;
       __threadfence_block();
     }
     int64_t dn = 0;

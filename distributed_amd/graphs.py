@@ -111,6 +111,90 @@ def random_dag(n_tasks: int, n_workers: int, *, seed: int = 0, fanin: int = 4,
         nbytes=nbytes, start=np.zeros(n), stop=stop, nthreads=nth))
 
 
+def _rows_dag(name, rows, n_roots, nbytes, rng, n_workers, n_inner_prefixes, random_durations, nthreads) -> dict:
+    """The graph dict of ``mixed_fanin_dag`` / ``layered_dag`` from their dependency rows: task
+    index = priority, the first ``n_roots`` tasks prefix "root", the others cycling through
+    the inner prefixes, durations and ``nthreads`` (an int, "random" = 1-4, or one value per
+    worker) drawn from ``rng`` after the rows."""
+    n = len(rows)
+    dep_ptr, dep_idx = _csr_from_rows(rows)
+    stop = rng.uniform(0.001, 0.1, n) if random_durations else np.full(n, 0.01)
+    if isinstance(nthreads, str):
+        if nthreads != "random":
+            raise ValueError(f"nthreads: an int, 'random' or an array, not {nthreads!r}")
+        nth = rng.integers(1, 5, n_workers)
+    elif np.ndim(nthreads) == 0:
+        nth = np.full(n_workers, int(nthreads))
+    else:
+        nth = np.asarray(nthreads)
+        if nth.shape != (int(n_workers),):
+            raise ValueError("nthreads: one value per worker")
+    k = int(n_inner_prefixes)
+    prefix_names = ["root"] + (["inner"] if k == 1 else [f"inner{j}" for j in range(k)])
+    prefix_id = np.zeros(n, np.int32)
+    prefix_id[n_roots:] = 1 + (np.arange(n_roots, n) % k)
+    group_names = [f"{p}-{TOKEN}" for p in prefix_names]
+    return _finish(dict(
+        name=name, dep_ptr=dep_ptr, dep_idx=dep_idx,
+        prio=np.arange(n, dtype=np.int64), prefix_id=prefix_id, group_id=prefix_id.copy(),
+        prefix_names=prefix_names, group_names=group_names,
+        group_prefix=np.arange(len(prefix_names)), prefix_default_dur=np.full(len(prefix_names), -1.0),
+        nbytes=nbytes, start=np.zeros(n), stop=stop, nthreads=nth))
+
+
+MIXED_FANINS = (1, 2, 3, 7, 8, 9, 10, 23, 24, 25, 26, 40)
+
+
+def mixed_fanin_dag(n_tasks: int, n_workers: int, *, seed: int = 0, fanins: tuple = MIXED_FANINS,
+                    root_frac: float = 0.1, window: int | None = None, n_inner_prefixes: int = 1,
+                    random_durations: bool = False, nthreads=1) -> dict:
+    """``random_dag`` with a fan-in of its own per task: every non-root task i draws its
+    fan-in k from ``fanins`` and then ``unique(rng.integers(max(0, i - window), i, k))``
+    dependencies (``window`` defaults to 4W). One graph then holds completing tasks with
+    long dependency lists whose dependents have short ones, and the other way round, which
+    a uniform fan-in cannot: the default tuple sits on both sides of the stream engine's
+    local-mode limits (8 dependencies of a frontier task, 24 of the completing task) and
+    past them. ``nthreads``: an int, "random" (1-4) or one value per worker."""
+    rng = np.random.default_rng(seed)
+    n = int(n_tasks)
+    r = max(1, int(n * root_frac))
+    win = int(window) if window is not None else 4 * int(n_workers)
+    nbytes = rng.lognormal(10, 2, n).astype(np.int64)
+    ks = rng.choice(np.asarray(fanins, np.int64), size=n - r)
+    rows = [[] for _ in range(r)]
+    for i, k in zip(range(r, n), ks.tolist()):
+        rows.append(np.unique(rng.integers(max(0, i - win), i, k)))
+    return _rows_dag(f"mixed_fanin_dag_{n}x{n_workers}", rows, r, nbytes, rng, n_workers, n_inner_prefixes,
+                     random_durations, nthreads)
+
+
+def layered_dag(n_layers: int, width: int, n_workers: int, *, seed: int = 0, fanins: tuple = (7, 8), span: int = 1,
+                n_inner_prefixes: int = 1, random_durations: bool = False, nthreads=1) -> dict:
+    """``n_layers`` layers of ``width`` tasks; layer 0 has no dependencies, every task of a
+    later layer draws its fan-in k from ``fanins`` and ``unique(rng.integers(0, width, k))``
+    dependencies in the layer before. A layer completes within one round, and the tasks of
+    the next become ready with their last dependency, so its late completions make several
+    tasks ready at once, each with k dependencies held by as many workers: stimuli with many
+    short dependency lists, which ``mixed_fanin_dag``'s chains do not give. ``fanins`` may be a
+    sequence of tuples, taken in turn by layers 1, 2, ... (a layer of short lists under one of
+    long ones: the completing task's own list then leaves the descriptor to the ready tasks).
+    ``span`` > 1 draws from that many layers before, so a task shares dependencies with the
+    tasks it depends on.
+    Other arguments as ``mixed_fanin_dag``."""
+    rng = np.random.default_rng(seed)
+    n = int(n_layers) * int(width)
+    nbytes = rng.lognormal(10, 2, n).astype(np.int64)
+    per_layer = [fanins] if np.ndim(fanins[0]) == 0 else list(fanins)
+    rows = [[] for _ in range(width)]
+    for layer in range(1, int(n_layers)):
+        ks = rng.choice(np.asarray(per_layer[(layer - 1) % len(per_layer)], np.int64), size=width)
+        back = min(int(span), layer) * width  # the tasks of the `span` layers before
+        for k in ks.tolist():
+            rows.append(layer * width - back + np.unique(rng.integers(0, back, k)))
+    return _rows_dag(f"layered_dag_{n_layers}x{width}x{n_workers}", rows, int(width), nbytes, rng, n_workers,
+                     n_inner_prefixes, random_durations, nthreads)
+
+
 def restrict(g: dict, frac: float, *, seed: int = 0, max_valid: int = 8, empty_frac: float = 0.1,
              loose_frac: float = 0.5) -> dict:
     """Worker restrictions on a fraction of the tasks (``TaskState.worker_restrictions`` /

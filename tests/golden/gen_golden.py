@@ -375,8 +375,9 @@ def fixtures():
                                                    nthreads="random"), inf),
         "c2var_sat2.5": (lambda: graphs.random_dag(4000, 32, seed=7, n_inner_prefixes=2, random_durations=True,
                                                    nthreads="random", root_frac=0.3), 2.5),
-        # more task prefixes than the stream engine's descriptors carry (PD = 8): the
-        # round-kernel engine's path
+        # more task prefixes than one descriptor's 8 durations serve: the stream engine's
+        # ``dring`` path, PD < P <= PX (8 < P <= 32). The round-kernel engine takes over past
+        # PX: the edge_p33 / edge_p40* / edge_p64 fixtures below
         "c2p12_sat1.1": (lambda: graphs.random_dag(3000, 64, seed=8, n_inner_prefixes=12, random_durations=True,
                                                    nthreads="random"), 1.1),
         "c2p12_satinf": (lambda: graphs.random_dag(2500, 48, seed=9, n_inner_prefixes=11, random_durations=True,
@@ -405,6 +406,67 @@ def fixtures():
         # empty valid sets that are not loose: no-worker, and everything downstream waits
         "restr_noworker_sat1.1": (lambda: graphs.restrict(graphs.random_dag(5000, 64, seed=57), 0.2, seed=58),
                                   1.1),
+        **edge_fixtures(),
+    }
+
+
+def edge_fixtures():
+    """The ``edge_*`` family: the shapes at which the engines change path. What makes each
+    one worth having is asserted from its graph and log by tests/test_edge_census.py."""
+    inf = math.inf
+
+    def var_dag(n, w, seed, k):  # the c2var shape with k inner prefixes (k + 1 prefixes)
+        return graphs.random_dag(n, w, seed=seed, n_inner_prefixes=k, random_durations=True, nthreads="random")
+
+    def mixed(n, w, seed, k=3, **kw):
+        kw.setdefault("nthreads", "random")
+        return graphs.mixed_fanin_dag(n, w, seed=seed, n_inner_prefixes=k, random_durations=True, **kw)
+
+    return {
+        # the prefix count at which the stream engine (P <= PX = 32) hands over to the
+        # round-kernel engine: the last stream count, the first round-engine count, a common
+        # one at both saturations, and _task_prefix_count_global at its 64 entries (PMAX_G)
+        "edge_p32_sat1.1": (lambda: var_dag(2000, 40, 61, 31), 1.1),
+        "edge_p33_sat1.1": (lambda: var_dag(2000, 40, 62, 32), 1.1),
+        "edge_p40_sat1.1": (lambda: var_dag(2000, 40, 63, 39), 1.1),
+        "edge_p40_satinf": (lambda: var_dag(2000, 40, 64, 39), inf),
+        "edge_p64_sat1.1": (lambda: var_dag(2000, 40, 65, 63), 1.1),
+        # the round engine with its workers in global memory (W > LDS_WORKERS_MAX = 1024)
+        "edge_p40_w1100_sat1.1": (lambda: var_dag(6000, 1100, 66, 39), 1.1),
+        # ... with restriction rows up to 12 wide
+        "edge_p40_restr_sat1.1": (lambda: graphs.restrict(var_dag(2000, 40, 67, 39), 0.3, seed=68, max_valid=12,
+                                                          empty_frac=0.0), 1.1),
+        # ... with stimuli that touch more than TOUCH_MAX = 24 workers and wide fan-ins
+        "edge_p40_mixed_sat1.1": (lambda: mixed(2500, 48, 69, 39), 1.1),
+        # the stream engine's local / global classification at its limits (dgp_stream.h
+        # build_desc): 24 / 25 dependencies of the completing task, 8 / 9 of a ready task, 64 /
+        # 65 descriptor entries, 32 / 33 workers touched
+        "edge_mixed_w48_sat1.1": (lambda: mixed(2500, 48, 70), 1.1),
+        "edge_mixed_w48_satinf": (lambda: mixed(2500, 48, 71), inf),
+        "edge_mixed_w200_sat1.1": (lambda: mixed(3000, 200, 74, window=200), 1.1),
+        # the two limits the mixed graphs reach only on stimuli that are global already (more
+        # than 8 or 24 dependencies): layers of 7-8 dependencies make stimuli that stay local
+        # up to 63 / 64 entries and trip at 65; short layers under them leave the descriptor
+        # to six ready tasks, whose holders reach 32 workers local and 33 global
+        "edge_layers_ne_sat1.1": (lambda: graphs.layered_dag(40, 64, 64, seed=300, fanins=(7, 8), n_inner_prefixes=3,
+                                                             random_durations=True, nthreads="random"), 1.1),
+        "edge_layers_tmax_sat1.1": (lambda: graphs.layered_dag(15, 200, 200, seed=302, fanins=((1, 2), (7, 8)),
+                                                               n_inner_prefixes=3, random_durations=True,
+                                                               nthreads="random"), 1.1),
+        # three workers that each need more remote dependencies than a needs_what table holds
+        # (63 on the stream engine: exact scans of processing_on), with local stimuli that
+        # place a ready task back on the completing worker, sharing dependencies with it
+        "edge_scan_refill_sat1.1": (lambda: graphs.layered_dag(15, 200, 3, seed=400, fanins=(7, 8), span=2,
+                                                               n_inner_prefixes=3, random_durations=True,
+                                                               nthreads="random"), 1.1),
+        # 64 / 65 staging rows: ceil(nthreads * 1.1) of 61, 62, 63, 64 and 71 next to 2
+        "edge_threads_sat1.1": (lambda: mixed(3000, 6, 73, fanins=(1, 2, 3, 4), root_frac=0.3,
+                                              nthreads=[55, 56, 57, 58, 64, 1]), 1.1),
+        # restriction rows of 8 and 9 valid workers (RC_MAX = 8)
+        "edge_restr_wide_sat1.1": (lambda: graphs.restrict(mixed(2000, 40, 72, fanins=(1, 2, 6, 8)), 0.4, seed=75,
+                                                           max_valid=20, empty_frac=0.0), 1.1),
+        # a one-worker cluster
+        "edge_w1_sat1.1": (lambda: graphs.random_dag(300, 1, seed=76, nthreads=3), 1.1),
     }
 
 

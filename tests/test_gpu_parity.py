@@ -12,6 +12,7 @@ import pytest
 
 from conftest import GOLDEN, golden_files
 from oracle import oracle
+from stimulus_census import max_worker_prefixes
 
 pytestmark = pytest.mark.gpu
 
@@ -134,7 +135,10 @@ def test_engine_full_c2(engine_cls):
 
 
 @pytest.mark.parametrize("window", [32, 64])
-@pytest.mark.parametrize("name", ["c2mini_sat1.1.npz", "c2var_sat1.1.npz", "restr_sat1.1.npz", "c3mini_sat1.1.npz"])
+@pytest.mark.parametrize("name", ["c2mini_sat1.1.npz", "c2var_sat1.1.npz", "restr_sat1.1.npz", "c3mini_sat1.1.npz",
+                                  "edge_mixed_w48_sat1.1.npz", "edge_threads_sat1.1.npz", "edge_restr_wide_sat1.1.npz",
+                                  "edge_p32_sat1.1.npz", "edge_layers_ne_sat1.1.npz", "edge_layers_tmax_sat1.1.npz",
+                                  "edge_scan_refill_sat1.1.npz"])
 def test_both_window_builds_match_fixture(engine_cls, name, window):
     """Each fixture on BOTH stream-kernel builds, forced (dgp_set_window: 32-slot window with
     wait-in-place claims; 64 slots, no wait-in-place): the auto choice runs restricted graphs
@@ -148,6 +152,176 @@ def test_both_window_builds_match_fixture(engine_cls, name, window):
         out = eng.placements()
         out.update(eng.snapshots(R))
     assert_same(out, exp, PL_KEYS + ROUND_KEYS)
+
+
+SWEEP_W = (31, 32, 33, 63, 64, 65)
+SWEEP_SAT = (1.0, 1.1, "inf")
+SWEEP_P = (4, 40)
+# one seed per case, none of them a fixture's (tests/golden/gen_golden.py uses 0..76, 300, 302
+# and 400; the layered test below 310 and 311). Each P = 40 case was checked on the oracle's
+# log to keep every worker within the engines' 8-prefix cap
+# (stimulus_census.max_worker_prefixes; the test asserts it again): a case that broke it would
+# get another seed here, never a skip
+SWEEP_SEED = {(p, w, s): 500 + i for i, (p, w, s) in enumerate(
+    (p, w, s) for p in SWEEP_P for w in SWEEP_W for s in SWEEP_SAT)}
+
+
+@pytest.mark.parametrize("n_prefixes", SWEEP_P)
+@pytest.mark.parametrize("w", SWEEP_W)
+def test_engine_matches_oracle_edge_sweep(engine_cls, w, n_prefixes):
+    """Fresh-seed mixed fan-in graphs against the oracle, which the edge_* fixtures pin to the
+    reference at these shapes (tests/test_oracle_golden.py): worker counts around 32 and 64,
+    three saturations, on the stream engine (4 prefixes) and on the round-kernel engine (40).
+    Placement log, every round's snapshot and the final states, bit for bit. (These graphs
+    sit on both sides of the 24- and 8-dependency limits; 64 entries and 32 touched workers
+    are reached by the layered graphs of the next test.)"""
+    from distributed_amd import graphs
+
+    for sat in SWEEP_SAT:
+        g = graphs.mixed_fanin_dag(1500, w, seed=SWEEP_SEED[n_prefixes, w, sat], n_inner_prefixes=n_prefixes - 1,
+                                   random_durations=True, nthreads="random")
+        cfg = {"bandwidth": 100_000_000, "default_data_size": 1024, "unknown_duration": 0.5, "saturation": sat}
+        ref = oracle.replay(g, cfg)
+        assert len(ref["pl_task"]) == g["n_tasks"]
+        if n_prefixes > 32:
+            assert max_worker_prefixes(g, ref) <= 8, (w, sat)
+        R = ref["n_rounds"] + 2
+        with engine_cls(0) as eng:
+            eng.load(g, cfg, snapshots=R)
+            eng.replay()
+            out = eng.placements()
+            out.update(eng.snapshots(R))
+            out["final_state"] = eng.task_states()
+            st = eng.stats()
+        try:
+            assert_same(out, ref, PL_KEYS + ROUND_KEYS)
+        except AssertionError as e:
+            raise AssertionError(f"W={w} P={n_prefixes} saturation={sat}: {e}") from None
+        assert np.array_equal(out["final_state"], ref["final_state"]), (w, sat)
+        # guard: which engine ran (dr_steps: the round engine's reservation steps)
+        assert (st["dr_steps"] > 0) == (n_prefixes > 32), (w, sat, st["dr_steps"])
+
+
+@pytest.mark.parametrize("seed", [310, 311])
+@pytest.mark.parametrize("shape", ["ne", "tmax", "scan"])
+def test_engine_matches_oracle_layered(engine_cls, shape, seed):
+    """Fresh seeds of the two layered shapes (fixtures edge_layers_*) against the oracle. The
+    oracle's log is first checked, by the prefetcher's own walk (stimulus_census), to hold
+    stimuli that stay local with exactly 64 descriptor entries next to ones that trip at 65,
+    that stay local with exactly 32 workers touched next to ones global by 33, or ("scan":
+    five 2-thread workers) local stimuli that refill a worker whose needs_what is in scan mode
+    with a task sharing dependencies with the completing one (scan_mode_refills)."""
+    from distributed_amd import graphs
+    from stimulus_census import REASONS, scan_mode_refills, stimulus_census
+
+    if shape == "scan":
+        g = graphs.layered_dag(15, 200, 5, seed=seed, fanins=(7, 8), span=2, n_inner_prefixes=3,
+                               random_durations=True, nthreads=2)
+    elif shape == "ne":
+        g = graphs.layered_dag(40, 64, 64, seed=seed, fanins=(7, 8), n_inner_prefixes=3, random_durations=True,
+                               nthreads="random")
+    else:
+        g = graphs.layered_dag(15, 200, 200, seed=seed, fanins=((1, 2), (7, 8)), n_inner_prefixes=3,
+                               random_durations=True, nthreads="random")
+    cfg = {"bandwidth": 100_000_000, "default_data_size": 1024, "unknown_duration": 0.5, "saturation": 1.1}
+    ref = oracle.replay(g, cfg)
+    c = stimulus_census(g, ref, 1.1)
+    loc = c["reason"] == REASONS.index("local")
+    if shape == "scan":
+        assert scan_mode_refills(g, ref, 1.1, 63)[0] >= 5
+    elif shape == "ne":
+        assert (loc & (c["n"] == 64)).any() and (c["trip_n"] == 65).any()
+    else:
+        assert (loc & (c["nt"] == 32)).any() and ((c["reason"] == REASONS.index("tmax")) & (c["nt"] == 33)).any()
+    R = ref["n_rounds"] + 2
+    with engine_cls(0) as eng:
+        eng.load(g, cfg, snapshots=R)
+        eng.replay()
+        out = eng.placements()
+        out.update(eng.snapshots(R))
+        out["final_state"] = eng.task_states()
+    assert_same(out, ref, PL_KEYS + ROUND_KEYS)
+    assert np.array_equal(out["final_state"], ref["final_state"])
+
+
+ROUND_ENGINE = ["edge_p33_sat1.1.npz", "edge_p40_sat1.1.npz", "edge_p40_satinf.npz", "edge_p64_sat1.1.npz",
+                "edge_p40_w1100_sat1.1.npz", "edge_p40_restr_sat1.1.npz", "edge_p40_mixed_sat1.1.npz"]
+
+
+@pytest.mark.parametrize("name", ROUND_ENGINE + ["edge_p32_sat1.1.npz"])
+def test_prefix_count_selects_the_engine(engine_cls, name):
+    """Guards only (the counters come from the code under test; what binds is
+    tests/test_edge_census.py and the parity above): more than 32 prefixes replay on the
+    round-kernel engine -- dgp_stats' dr_steps and global_stimuli are counted by its commit
+    alone, the stream engine leaves both at 0 -- and exactly 32 still on the stream engine.
+    On the mixed fan-in fixture both of the round engine's paths ran: stimuli committed by
+    reservation and global ones."""
+    g, cfg, exp, meta = oracle.load_fixture(os.path.join(GOLDEN, name))
+    with engine_cls(0) as eng:
+        eng.load(g, cfg)
+        n = eng.replay()
+        st = eng.stats()
+    assert n == len(exp["pl_task"])
+    if name in ROUND_ENGINE:
+        assert st["dr_steps"] > 0
+        assert st["global_stimuli"] < n
+        if name == "edge_p40_mixed_sat1.1.npz":
+            assert st["global_stimuli"] > 0
+    else:
+        assert st["dr_steps"] == 0 and st["global_stimuli"] == 0
+
+
+def _prefix_groups(n_prefixes, group_size=3):
+    """Dependency-free tasks in small groups, one prefix per group, on one 16-thread worker:
+    update_graph places them all through decide_worker_non_rootish's no-dependency fast path
+    (a group of 3 is not root-ish), so the worker processes ``n_prefixes`` distinct prefixes."""
+    from distributed_amd import graphs
+
+    n = n_prefixes * group_size
+    rng = np.random.default_rng(7)
+    names = [f"load{k}" for k in range(n_prefixes)]
+    gid = np.arange(n) // group_size
+    return graphs._finish(dict(
+        name=f"prefix_groups_{n_prefixes}", dep_ptr=np.zeros(n + 1, np.int64), dep_idx=np.zeros(0, np.int32),
+        prio=np.arange(n), prefix_id=gid, group_id=gid, prefix_names=names,
+        group_names=[f"{p}-{graphs.TOKEN}" for p in names], group_prefix=np.arange(n_prefixes),
+        prefix_default_dur=np.full(n_prefixes, -1.0), nbytes=rng.integers(1, 10_000, n), start=np.zeros(n),
+        stop=rng.uniform(0.001, 0.2, n), nthreads=[16]))
+
+
+def test_more_than_8_prefixes_on_a_worker_is_an_error_not_a_placement(engine_cls):
+    """The documented cap (README: more than 8 prefixes processing on one worker ends GPU
+    placement): 8 prefixes on one worker equal the oracle bit for bit; 9 make the replay
+    return DGP_E_DEVICE -- update_graph runs to its end with the error in the control block
+    and dgp_run_rounds reads it before it launches anything -- and after dgp_reset the same
+    engine replays the 8-prefix graph correctly."""
+    from distributed_amd import _lib
+
+    cfg = {"bandwidth": 100_000_000, "default_data_size": 1024, "unknown_duration": 0.5, "saturation": "inf"}
+    g8, g9 = _prefix_groups(8), _prefix_groups(9)
+    ref = oracle.replay(g8, cfg)
+    assert (ref["pl_route"] == 3).all() and ref["round_nproc"][0].tolist() == [24]
+    R = ref["n_rounds"] + 2
+    with engine_cls(0) as eng:
+        eng.load(g8, cfg, snapshots=R)
+        eng.replay()
+        out = eng.placements()
+        out.update(eng.snapshots(R))
+        out["final_state"] = eng.task_states()
+    assert_same(out, ref, PL_KEYS + ROUND_KEYS)
+    assert np.array_equal(out["final_state"], ref["final_state"])
+    with engine_cls(0) as eng:
+        eng.load(g9, cfg)
+        with pytest.raises(_lib.DgpError, match=r"failed \(-4\).*PMAX") as ei:  # DGP_E_DEVICE
+            eng.replay()
+        assert "device engine error 1 " in str(ei.value)
+        eng.reset()
+        eng.set_graph(g8)
+        assert eng.replay() == 24
+        out = eng.placements()
+        out["final_state"] = eng.task_states()
+    assert_same(out, ref, PL_KEYS)
+    assert np.array_equal(out["final_state"], ref["final_state"])
 
 
 @pytest.mark.parametrize("window", [32, 64])

@@ -90,8 +90,11 @@ def test_service_matches_reference_fixture(name, per_message):
     assert np.array_equal(out["final_state"], exp["final_state"])
 
 
+# edge_p40 has more prefixes than the resident kernel takes: set_resident(True) must still
+# answer it correctly, through the launch path of the round-kernel engine
 RESIDENT = ["c2var_sat1.1.npz", "c2mini_satinf.npz", "c3mini_sat1.1.npz", "restr_sat1.1.npz", "c2p12_sat1.1.npz",
-            "svc_c2var_sat1.1.npz"]
+            "svc_c2var_sat1.1.npz", "edge_mixed_w48_sat1.1.npz", "edge_threads_sat1.1.npz", "edge_p40_sat1.1.npz",
+            "edge_scan_refill_sat1.1.npz"]
 
 
 @pytest.mark.parametrize("per_message", [True, False], ids=["per-message", "per-round"])
@@ -108,8 +111,41 @@ def test_resident_service_matches_reference_fixture(name, per_message):
     assert np.array_equal(out["final_state"], exp["final_state"])
 
 
+ROUND_ENGINE = ["edge_p33_sat1.1.npz", "edge_p40_sat1.1.npz", "edge_p40_satinf.npz", "edge_p64_sat1.1.npz",
+                "edge_p40_w1100_sat1.1.npz", "edge_p40_restr_sat1.1.npz", "edge_p40_mixed_sat1.1.npz"]
+
+
+@pytest.mark.parametrize("name", ROUND_ENGINE + ["edge_p32_sat1.1.npz"])
+def test_service_prefix_count_selects_the_engine(name):
+    """A guard, not the binding check: with more than 32 prefixes each batch is one round of
+    the round-kernel engine, launches of k_frontier_release and k_candidate_commbytes
+    (dgp_kernel_times ids 0 and 1) in every call; with 32 the stream kernel answers and neither is
+    launched."""
+    from distributed_amd.engine import PlacementEngine
+
+    round_engine = name in ROUND_ENGINE
+    g, cfg, exp, meta = oracle.load_fixture(os.path.join(GOLDEN, name))
+    assert (len(g["prefix_default_dur"]) > 32) == round_engine
+    msgs, ptr = fixture_messages(g, exp)
+    calls = sum(1 for k in range(len(ptr) - 1) if ptr[k + 1] > ptr[k])
+    with PlacementEngine(0) as eng:
+        eng.load(g, cfg, snapshots=len(exp["round_nplaced"]) + 2, results=False)
+        eng.set_timing(True)
+        eng.update_graph()
+        status = drive(eng, msgs, ptr, per_message=False)
+        kt = eng.kernel_times()
+        out = eng.placements()
+    assert (status == 0).all()
+    assert_same(out, exp, PL_KEYS)
+    n0, n1 = kt["frontier_release"][1], kt["candidate_commbytes"][1]
+    # a batch whose answers depend on its own stimuli runs in several segments: at least one
+    # launch per call
+    assert (n0 == n1 >= calls > 0) if round_engine else (n0 == n1 == 0), kt
+
+
 @pytest.mark.parametrize("resident", [False, True], ids=["launch", "resident"])
-@pytest.mark.parametrize("name", ["c2var_sat1.1.npz", "restr_sat1.1.npz", "c3mini_sat1.1.npz"])
+@pytest.mark.parametrize("name", ["c2var_sat1.1.npz", "restr_sat1.1.npz", "c3mini_sat1.1.npz",
+                                  "edge_mixed_w48_sat1.1.npz"])
 def test_window_switched_between_calls(name, resident):
     """Both stream-kernel builds on ONE engine (dgp_set_window, ABI 19): the window alternates
     32 / 64 every call, so consecutive batches run on different builds over the same resident
