@@ -92,9 +92,15 @@ SIGNATURES = {
     "dgp_sync_workers": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dgp_sync_globals": (C.c_int, [_P, C.c_int64, C.c_double, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, C.c_double,
                                    _P, _P, _P]),
+    "dgp_audit_state": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    "dgp_audit_tasks": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
+    "dgp_audit_workers": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P,
+                                    _P]),
+    "dgp_audit_globals": (C.c_int, [_P, C.c_int64, C.c_double, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, C.c_double,
+                                    _P, _P, _P, C.c_int64, _P, _P]),
 }
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 _libs: dict = {}
 
 

@@ -36,6 +36,7 @@ def settings() -> dict:
     cfg = _dask_config()
     return dict(enabled=bool(cfg.get(f"{KEY}.enabled")), stealing=bool(cfg.get(f"{KEY}.stealing")),
                 device=int(cfg.get(f"{KEY}.device")), validate=bool(cfg.get(f"{KEY}.validate")),
+                audit_interval=float(cfg.get(f"{KEY}.audit-interval") or 0),
                 work_stealing=bool(cfg.get("distributed.scheduler.work-stealing")))
 
 
@@ -56,7 +57,8 @@ def scheduler_extensions(base: dict | None = None) -> dict:
 
         if st["stealing"] and st["work_stealing"]:
             ext["stealing"] = functools.partial(GPUWorkStealing, device=st["device"], validate=st["validate"])
-        ext["gpu-placement"] = functools.partial(GPUPlacementExtension, device=st["device"], validate=st["validate"])
+        ext["gpu-placement"] = functools.partial(GPUPlacementExtension, device=st["device"], validate=st["validate"],
+                                                 audit_interval=st["audit_interval"])
     return ext
 
 
@@ -84,5 +86,5 @@ def install(scheduler) -> dict:
         exts["stealing"] = done["stealing"] = GPUWorkStealing(scheduler, device=st["device"], validate=st["validate"])
     if not isinstance(exts.get("gpu-placement"), GPUPlacementExtension):
         exts["gpu-placement"] = done["gpu-placement"] = GPUPlacementExtension(
-            scheduler, device=st["device"], validate=st["validate"])
+            scheduler, device=st["device"], validate=st["validate"], audit_interval=st["audit_interval"])
     return done

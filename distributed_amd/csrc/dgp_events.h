@@ -654,7 +654,14 @@ __global__ void __launch_bounds__(64) k_ev_release_tasks(const Dev* __restrict__
     for (int i = 0; i < n && c->error == 0; i++) {
       const int t = task[i];
       const uint8_t st = D.state[t];
-      if (st == S_RELEASED) continue;  // on to forgotten: the flag only
+      // a forgotten task leaves its TaskGroup's states["released"] (TaskState.state's setter,
+      // :2853-2881): the host set TF_FORGOTTEN on the tasks this call forgets (each listed once,
+      // none forgotten before), so the group count loses them here
+      const bool forgotten = (D.tflags[t] & TF_FORGOTTEN) != 0;
+      if (st == S_RELEASED) {  // on to forgotten: the flag, and the group's count
+        if (forgotten) atomicAdd((unsigned long long*)&D.g_relwait[D.group[t]], (unsigned long long)-1ll);
+        continue;
+      }
       if (st == S_MEMORY) {
         const int64_t nb = nbv(D, D.res_nbytes[t]);
         for (int b = 0; b < D.WB; b++) {
@@ -691,7 +698,9 @@ __global__ void __launch_bounds__(64) k_ev_release_tasks(const Dev* __restrict__
         set_error(D, ERR_UNSUPPORTED, t);
         break;
       }
-      if (st != S_WAITING) atomicAdd((unsigned long long*)&D.g_relwait[D.group[t]], 1ull);  // released + waiting
+      // released + waiting: a waiting task was counted already; a forgotten one is in neither
+      const long long dg = (st != S_WAITING ? 1 : 0) - (forgotten ? 1 : 0);
+      if (dg) atomicAdd((unsigned long long*)&D.g_relwait[D.group[t]], (unsigned long long)dg);
       D.state[t] = S_RELEASED;
     }
     if (S.error) set_error(D, S.error, S.err_task);

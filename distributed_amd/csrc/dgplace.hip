@@ -40,6 +40,7 @@
 #include "dgp_events.h"
 #include "dgp_steal.h"
 #include "dgp_service.h"
+#include "dgp_audit.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -121,6 +122,8 @@ struct dgp_engine {
   size_t d_ev_cap = 0;
   char* d_msgbuf = nullptr;                // dgp_task_messages scratch (device)
   size_t d_msgbuf_cap = 0;
+  char* d_audit = nullptr;                 // dgp_audit_state scratch arena (device): grows with N, W, P
+  size_t d_audit_cap = 0;
   // resident service mode (dgp_set_resident): the stream kernel stays launched between
   // dgp_tasks_finished calls and takes each batch from a mailbox in pinned host memory
   dgp::svc::Mbox* mb = nullptr;      // host address
@@ -672,6 +675,7 @@ void dgp_destroy(dgp_engine* e) {
   if (e->h_msgs) (void)hipHostFree(e->h_msgs);
   if (e->d_ev) (void)hipFree(e->d_ev);
   if (e->d_msgbuf) (void)hipFree(e->d_msgbuf);
+  if (e->d_audit) (void)hipFree(e->d_audit);
   if (e->steal.arena) (void)hipFree(e->steal.arena);
   (void)hipFree(e->ctl);
   (void)hipFree(e->d_aux);
@@ -2437,6 +2441,12 @@ int dgp_release_tasks(dgp_engine* e, int64_t n, const int32_t* task, const uint8
   if (n < 0 || (n > 0 && (!task || !forget))) return fail(e, DGP_E_ARG, "dgp_release_tasks: bad batch");
   for (int64_t i = 0; i < n; i++)
     if (task[i] < 0 || task[i] >= D.N) return fail(e, DGP_E_ARG, "dgp_release_tasks: task out of range");
+  {  // each task once: a second visit would take a forgotten task out of its group's count again
+    std::vector<int32_t> once(task, task + n);
+    std::sort(once.begin(), once.end());
+    if (std::adjacent_find(once.begin(), once.end()) != once.end())
+      return fail(e, DGP_E_ARG, "dgp_release_tasks: a task listed twice");
+  }
   HIPCHK(e, hipSetDevice(e->device));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   // results in memory, released tasks and cancelled work (waiting, processing, queued,
@@ -2966,6 +2976,438 @@ int dgp_sync_globals(dgp_engine* e, int64_t n_tasks_counter, double network_occ_
   e->pending_resync = false;  // the resync is complete (dgp_sync_globals comes last)
   e->pending_lo = -1;
   return 0;
+}
+
+// The state audit (include/dgplace.h, dgp_audit.h). Nothing of the engine changes: the
+// readiness test is event_ready's without its mode switch, the recount lives in an arena of
+// its own, and the only host fields touched are that arena's pointer and size.
+int dgp_audit_state(dgp_engine* e, int64_t cap, dgp_violation* out, int64_t* n_violations, int64_t* n_skipped) {
+  if (int rc_ = resident_stop(e)) return rc_;
+  if (!e) return DGP_E_ARG;
+  if (n_violations) *n_violations = 0;
+  if (n_skipped) *n_skipped = 0;
+  if (cap < 0 || (cap > 0 && !out) || !n_violations) return fail(e, DGP_E_ARG, "dgp_audit_state: bad output arguments");
+  if (!e->graph_done) return fail(e, DGP_E_STATE, "dgp_update_graph first");
+  if (e->pending_resync)
+    return fail(e, DGP_E_STATE, "dgp_audit_state: a resync is pending (the state is the scheduler's to hand over)");
+  if (e->mode == 1)
+    return fail(e, DGP_E_STATE, "dgp_audit_state: engine advanced by a replay (dgp_run_rounds): its state is not "
+                                "canonical between rounds");
+  const dgp::Dev& D = e->D;
+  if (!(D.P <= dgp::st::PX) || !D.gw_needs_saved)
+    return fail(e, DGP_E_STATE, "dgp_audit_state: the round-kernel engine (more than 32 prefixes) has no state audit");
+  namespace AU = dgp::audit;
+  HIPCHK(e, hipSetDevice(e->device));
+  const size_t N = (size_t)D.N, W = (size_t)D.W, P = (size_t)D.P, G = (size_t)D.G;
+  // the arena: [zeroed counters | host inputs | violation records], each part 16-byte aligned
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off += (bytes + 15) & ~(size_t)15;
+    return o;
+  };
+  const size_t o_nproc = take(W * 4), o_lr = take(W * 4), o_wp = take(W * P * 4), o_needs = take(W * AU::NE * 4),
+               o_ent = take(W * AU::NE * 4), o_qseen = take(N * 4), o_nbytes = take(W * 8), o_grp = take(G * 8),
+               o_gsum = take(P * 8), o_tot = take(8 * 8), o_scan = take(W), o_nviol = take(8);
+  const size_t zero_bytes = off;
+  const size_t o_status = take(W), o_bcap = take(W * 4), o_out = take((size_t)cap * sizeof(dgp_violation));
+  if (off > e->d_audit_cap) {
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (e->d_audit) (void)hipFree(e->d_audit);
+    e->d_audit = nullptr;
+    e->d_audit_cap = 0;
+    HIPCHK(e, hipMalloc((void**)&e->d_audit, off));
+    e->d_audit_cap = off;
+  }
+  char* B = e->d_audit;
+  AU::Scratch A{};
+  A.c_nproc = (int32_t*)(B + o_nproc);
+  A.c_lr = (int32_t*)(B + o_lr);
+  A.c_wp = (int32_t*)(B + o_wp);
+  A.c_needs = (int32_t*)(B + o_needs);
+  A.n_ent = (uint32_t*)(B + o_ent);
+  A.c_qseen = (int32_t*)(B + o_qseen);
+  A.c_nbytes = (int64_t*)(B + o_nbytes);
+  A.c_grp = (int64_t*)(B + o_grp);
+  A.c_gsum = (int64_t*)(B + o_gsum);
+  A.c_tot = (int64_t*)(B + o_tot);
+  A.scan = (uint8_t*)(B + o_scan);
+  A.n_viol = (unsigned long long*)(B + o_nviol);
+  A.status = (const uint8_t*)(B + o_status);
+  A.base_cap = (const int32_t*)(B + o_bcap);
+  A.out = (dgp_violation*)(B + o_out);
+  A.cap = cap;
+  std::vector<int32_t> bcap(W);
+  for (size_t w = 0; w < W; w++) {  // the cap rule of dgp_sync_workers
+    const int32_t nt = std::max<int32_t>(e->nthreads[w], 1);
+    bcap[w] = D.sat_inf ? 0 : std::max((int32_t)std::ceil(D.saturation * nt), (int32_t)1);
+  }
+  if (int rc = sync_dev(e)) return rc;
+  HIPCHK(e, hipMemsetAsync(B, 0, zero_bytes, e->stream));
+  HIPCHK(e, hipMemcpyAsync(B + o_status, e->paused_h.data(), W, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemcpyAsync(B + o_bcap, bcap.data(), W * 4, hipMemcpyHostToDevice, e->stream));
+  const dim3 blk(256);
+  auto launch = [&] {
+    hipLaunchKernelGGL(AU::k_au_needs, dim3(grid_for((int64_t)W * 64, 256, 2048)), blk, 0, e->stream, e->d_dev, A);
+    hipLaunchKernelGGL(AU::k_au_queue, dim3(grid_for((int64_t)N, 256, 2048)), blk, 0, e->stream, e->d_dev, A);
+    hipLaunchKernelGGL(AU::k_au_tasks, dim3(grid_for((int64_t)N, 256, 2048)), blk, 0, e->stream, e->d_dev, A);
+    hipLaunchKernelGGL(AU::k_au_workers, dim3(grid_for((int64_t)W * AU::NE, 256, 2048)), blk, 0, e->stream, e->d_dev,
+                       A);
+    hipLaunchKernelGGL(AU::k_au_globals, dim3(grid_for((int64_t)G, 256, 2048)), blk, 0, e->stream, e->d_dev, A);
+  };
+  if (e->timing) {  // dgp_set_timing: HIP events around the five launches, kernel-time id 7
+    if (int rc = timed_launch(e, 7, launch)) return rc;
+  } else {
+    launch();
+    HIPCHK(e, hipGetLastError());
+  }
+  unsigned long long total = 0;
+  int64_t tot[8];
+  HIPCHK(e, hipMemcpyAsync(&total, A.n_viol, 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipMemcpyAsync(tot, A.c_tot, sizeof tot, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  const int64_t kept = (int64_t)std::min<unsigned long long>(total, (unsigned long long)cap);
+  if (kept) {
+    HIPCHK(e, hipMemcpy(out, A.out, (size_t)kept * sizeof(dgp_violation), hipMemcpyDeviceToHost));
+    std::sort(out, out + kept, [](const dgp_violation& a, const dgp_violation& b) {
+      if (a.rule != b.rule) return a.rule < b.rule;
+      if (a.field != b.field) return a.field < b.field;
+      if (a.index != b.index) return a.index < b.index;
+      if (a.sub != b.sub) return a.sub < b.sub;
+      if (a.device_value != b.device_value) return a.device_value < b.device_value;
+      return a.expected_value < b.expected_value;
+    });
+  }
+  *n_violations = (int64_t)total;
+  if (n_skipped) *n_skipped = tot[4];
+  return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// One dgp_audit_tasks / _workers / _globals call: the arrays the resync would write are
+// staged in one blob, each with the device array it is compared against (k_au_cmp), plus the
+// queue / needs_what comparisons and what only the host holds.
+struct RowAudit {
+  static constexpr size_t NONE = ~(size_t)0;
+  struct Job {
+    int kind;  // 0 k_au_cmp, 1 k_au_row_queue, 2 k_au_row_needs
+    const void* dev;
+    size_t expect, idx, lim_exp;
+    long long n;
+    int div, esz, rule, field, sub;
+    uint64_t mask;
+    const int32_t* lim_dev;
+  };
+  std::vector<char> blob;
+  std::vector<Job> jobs;
+  std::vector<dgp_violation> host;  // fields the engine keeps on the host
+  size_t put(const void* p, size_t bytes) {
+    const size_t o = blob.size();
+    blob.resize(o + ((bytes + 15) & ~(size_t)15));
+    if (bytes) memcpy(blob.data() + o, p, bytes);
+    return o;
+  }
+  void cmp(const void* dev, const void* expect, long long n, int esz, int rule, int field, size_t idx = NONE,
+           int div = 1, uint64_t mask = ~0ull, int sub = -1, const int32_t* lim_dev = nullptr, size_t lim_exp = NONE) {
+    if (n <= 0) return;
+    jobs.push_back(Job{0, dev, put(expect, (size_t)n * esz), idx, lim_exp, n, div, esz, rule, field, sub, mask, lim_dev});
+  }
+};
+
+// event_ready without its mode switch (the audits change nothing); a pending resync is when
+// the rows arrive, so it does not refuse
+int row_audit_ready(dgp_engine* e, const char* what, int64_t cap, dgp_violation* out, int64_t* n_violations) {
+  if (!e) return DGP_E_ARG;
+  if (n_violations) *n_violations = 0;
+  if (cap < 0 || (cap > 0 && !out) || !n_violations) return fail(e, DGP_E_ARG, std::string(what) + ": bad output arguments");
+  if (!e->graph_done) return fail(e, DGP_E_STATE, "dgp_update_graph first");
+  if (e->mode == 1) return fail(e, DGP_E_STATE, "engine advanced by a replay (dgp_run_rounds); dgp_reset first");
+  if (!(e->D.P <= dgp::st::PX) || !e->D.gw_needs_saved)
+    return fail(e, DGP_E_STATE, std::string(what) + ": the round-kernel engine (more than 32 prefixes) has no state audit");
+  HIPCHK(e, hipSetDevice(e->device));
+  return 0;
+}
+
+int row_audit_run(dgp_engine* e, RowAudit& R, int64_t cap, dgp_violation* out, int64_t* n_violations) {
+  namespace AU = dgp::audit;
+  const size_t o_out = 16, o_blob = o_out + (((size_t)cap * sizeof(dgp_violation) + 15) & ~(size_t)15);
+  const size_t need = o_blob + R.blob.size() + 16;
+  if (need > e->d_audit_cap) {
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (e->d_audit) (void)hipFree(e->d_audit);
+    e->d_audit = nullptr;
+    e->d_audit_cap = 0;
+    HIPCHK(e, hipMalloc((void**)&e->d_audit, need));
+    e->d_audit_cap = need;
+  }
+  char* B = e->d_audit;
+  AU::Scratch A{};
+  A.n_viol = (unsigned long long*)B;
+  A.out = (dgp_violation*)(B + o_out);
+  A.cap = cap;
+  if (int rc = sync_dev(e)) return rc;
+  HIPCHK(e, hipMemsetAsync(B, 0, 16, e->stream));
+  if (!R.blob.empty())
+    HIPCHK(e, hipMemcpyAsync(B + o_blob, R.blob.data(), R.blob.size(), hipMemcpyHostToDevice, e->stream));
+  const dim3 blk(256);
+  for (const RowAudit::Job& j : R.jobs) {
+    const char* x = B + o_blob + j.expect;
+    const int32_t* idx = j.idx == RowAudit::NONE ? nullptr : (const int32_t*)(B + o_blob + j.idx);
+    const int32_t* le = j.lim_exp == RowAudit::NONE ? nullptr : (const int32_t*)(B + o_blob + j.lim_exp);
+    const dim3 grid(grid_for(j.n, 256, 2048));
+    if (j.kind == 1)
+      hipLaunchKernelGGL(AU::k_au_row_queue, grid, blk, 0, e->stream, e->d_dev, (const int32_t*)x, j.n, A);
+    else if (j.kind == 2)
+      hipLaunchKernelGGL(AU::k_au_row_needs, dim3(grid_for((int64_t)e->D.W * 64, 256, 2048)), blk, 0, e->stream, e->d_dev,
+                         (const int64_t*)x, (const uint32_t*)(B + o_blob + j.idx), A);
+    else if (j.esz == 1)
+      hipLaunchKernelGGL(AU::k_au_cmp<uint8_t>, grid, blk, 0, e->stream, (const uint8_t*)j.dev, (const uint8_t*)x, idx, j.n,
+                         j.div, (uint8_t)j.mask, j.rule, j.field, j.sub, j.lim_dev, le, A);
+    else if (j.esz == 4)
+      hipLaunchKernelGGL(AU::k_au_cmp<int32_t>, grid, blk, 0, e->stream, (const int32_t*)j.dev, (const int32_t*)x, idx, j.n,
+                         j.div, (int32_t)j.mask, j.rule, j.field, j.sub, j.lim_dev, le, A);
+    else
+      hipLaunchKernelGGL(AU::k_au_cmp<int64_t>, grid, blk, 0, e->stream, (const int64_t*)j.dev, (const int64_t*)x, idx, j.n,
+                         j.div, (int64_t)j.mask, j.rule, j.field, j.sub, j.lim_dev, le, A);
+  }
+  HIPCHK(e, hipGetLastError());
+  unsigned long long total = 0;
+  HIPCHK(e, hipMemcpyAsync(&total, A.n_viol, 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  int64_t kept = (int64_t)std::min<unsigned long long>(total, (unsigned long long)cap);
+  if (kept) HIPCHK(e, hipMemcpy(out, A.out, (size_t)kept * sizeof(dgp_violation), hipMemcpyDeviceToHost));
+  for (const dgp_violation& v : R.host) {
+    if (kept < cap) out[kept++] = v;
+    total++;
+  }
+  std::sort(out, out + kept, [](const dgp_violation& a, const dgp_violation& b) {
+    if (a.rule != b.rule) return a.rule < b.rule;
+    if (a.field != b.field) return a.field < b.field;
+    if (a.index != b.index) return a.index < b.index;
+    if (a.sub != b.sub) return a.sub < b.sub;
+    if (a.device_value != b.device_value) return a.device_value < b.device_value;
+    return a.expected_value < b.expected_value;
+  });
+  *n_violations = (int64_t)total;
+  return 0;
+}
+
+int64_t dbits(double x) {
+  int64_t v;
+  memcpy(&v, &x, 8);
+  return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dgp_audit_tasks(dgp_engine* e, int64_t n, const int32_t* task, const uint8_t* state, const int32_t* remaining,
+                    const int32_t* waiters, const int32_t* processing_on, const int64_t* nbytes,
+                    const uint8_t* long_running, const uint8_t* wanted, const int64_t* holder_ptr,
+                    const int32_t* holder_idx, int64_t cap, dgp_violation* out, int64_t* n_violations) {
+  if (int rc_ = resident_stop(e)) return rc_;
+  if (int rc = row_audit_ready(e, "dgp_audit_tasks", cap, out, n_violations)) return rc;
+  if (n < 0 || (n > 0 && (!task || !state || !remaining || !waiters || !processing_on || !nbytes || !long_running ||
+                          !wanted || !holder_ptr)))
+    return fail(e, DGP_E_ARG, "dgp_audit_tasks: bad rows");
+  if (n == 0) return 0;
+  const dgp::Dev& D = e->D;
+  const int64_t H = holder_ptr[n];
+  if (holder_ptr[0] != 0 || H < 0 || (H > 0 && !holder_idx)) return fail(e, DGP_E_ARG, "dgp_audit_tasks: holder_ptr");
+  const size_t WB = (size_t)D.WB;
+  // what k_sync_tasks would write, per column; the columns a kernel reads only in some states
+  // are compared for the rows in those states (include/dgplace.h)
+  std::vector<int32_t> t_all(n), po(n), t_act, rem_act, t_mem, t_ho, ho, t_multi;
+  std::vector<uint8_t> st(n), lr(n), tf(n), multi;
+  std::vector<int64_t> cur_mem;
+  std::vector<uint64_t> rows((size_t)n * WB, 0);
+  for (int64_t i = 0; i < n; i++) {
+    const int32_t t = task[i];
+    if (t < 0 || t >= D.N || state[i] > dgp::S_ERRED + 1 || holder_ptr[i + 1] < holder_ptr[i])
+      return fail(e, DGP_E_ARG, "dgp_audit_tasks: task / state / holder_ptr");
+    if (state[i] == dgp::S_PROCESSING && (processing_on[i] < 0 || processing_on[i] >= D.W))
+      return fail(e, DGP_E_ARG, "dgp_audit_tasks: processing task without a worker");
+    int first = -1;
+    for (int64_t k = holder_ptr[i]; k < holder_ptr[i + 1]; k++) {
+      const int w = holder_idx[k];
+      if (w < 0 || w >= D.W) return fail(e, DGP_E_ARG, "dgp_audit_tasks: holder out of range");
+      rows[(size_t)i * WB + (w >> 6)] |= 1ull << (w & 63);
+      if (first < 0) first = w;
+    }
+    const bool forgotten = state[i] == dgp::S_ERRED + 1;
+    const uint8_t s = forgotten ? (uint8_t)dgp::S_RELEASED : state[i];
+    const int64_t hn = holder_ptr[i + 1] - holder_ptr[i];
+    t_all[i] = t;
+    st[i] = s;
+    po[i] = s == dgp::S_PROCESSING ? processing_on[i] : -1;
+    lr[i] = long_running[i] ? dgp::TD_LR : 0;
+    tf[i] = (uint8_t)((wanted[i] ? dgp::TF_WANTED : 0) | (forgotten ? dgp::TF_FORGOTTEN : 0));
+    if (s == dgp::S_WAITING || s == dgp::S_PROCESSING || s == dgp::S_QUEUED || s == dgp::S_NO_WORKER) {
+      t_act.push_back(t);
+      rem_act.push_back(remaining[i]);
+    }
+    if (s == dgp::S_MEMORY) {
+      t_mem.push_back(t);
+      cur_mem.push_back(nbytes[i] >= 0 ? nbytes[i] : D.default_data_size);
+    }
+    if (s == dgp::S_PROCESSING || (s == dgp::S_MEMORY && hn == 1)) {
+      t_ho.push_back(t);
+      ho.push_back(s == dgp::S_PROCESSING ? processing_on[i] : first);
+    }
+    if (hn > 1) {
+      t_multi.push_back(t);
+      multi.push_back(dgp::TD_MULTI);
+    }
+  }
+  RowAudit R;
+  const int RT = DGP_AR_ROW_TASKS;
+  const size_t ia = R.put(t_all.data(), (size_t)n * 4);
+  R.cmp(D.state, st.data(), n, 1, RT, DGP_AF_STATE, ia);
+  R.cmp(D.waiters, waiters, n, 4, RT, DGP_AF_WAITERS, ia);
+  R.cmp(D.proc_on, po.data(), n, 4, RT, DGP_AF_PROC_ON, ia);
+  R.cmp(D.res_nbytes, nbytes, n, 8, RT, DGP_AF_RES_NBYTES, ia);
+  R.cmp(D.holders, rows.data(), n * (int64_t)WB, 8, RT, DGP_AF_WHO_HAS, ia, (int)WB, ~0ull, 0);  // sub = the word
+  R.cmp(D.tdyn, lr.data(), n, 1, RT, DGP_AF_LR, ia, 1, dgp::TD_LR);
+  R.cmp(D.tflags, tf.data(), n, 1, RT, DGP_AF_WANTED, ia, 1, dgp::TF_WANTED);
+  R.cmp(D.tflags, tf.data(), n, 1, RT, DGP_AF_FORGOTTEN, ia, 1, dgp::TF_FORGOTTEN);
+  if (!t_act.empty())
+    R.cmp(D.remaining, rem_act.data(), (long long)t_act.size(), 4, RT, DGP_AF_REMAINING, R.put(t_act.data(), t_act.size() * 4));
+  if (!t_mem.empty())
+    R.cmp(D.cur_nbytes, cur_mem.data(), (long long)t_mem.size(), 8, RT, DGP_AF_CUR_NBYTES, R.put(t_mem.data(), t_mem.size() * 4));
+  if (!t_ho.empty())
+    R.cmp(D.holder_of, ho.data(), (long long)t_ho.size(), 4, RT, DGP_AF_HOLDER_OF, R.put(t_ho.data(), t_ho.size() * 4));
+  if (!t_multi.empty())
+    R.cmp(D.tdyn, multi.data(), (long long)t_multi.size(), 1, RT, DGP_AF_MULTI, R.put(t_multi.data(), t_multi.size() * 4), 1,
+          dgp::TD_MULTI);
+  return row_audit_run(e, R, cap, out, n_violations);
+}
+
+int dgp_audit_workers(dgp_engine* e, int32_t n_workers, const int8_t* status, const int32_t* nproc,
+                      const int32_t* n_long_running, const int32_t* plen, const int32_t* prefix, const int32_t* count,
+                      const int64_t* netocc, const int64_t* nbytes, const uint8_t* idle, const uint8_t* saturated,
+                      const int64_t* needs_ptr, const int32_t* needs_task, const int32_t* needs_count, int64_t cap,
+                      dgp_violation* out, int64_t* n_violations) {
+  if (int rc_ = resident_stop(e)) return rc_;
+  if (int rc = row_audit_ready(e, "dgp_audit_workers", cap, out, n_violations)) return rc;
+  const dgp::Dev& D = e->D;
+  namespace S = dgp::st;
+  const int W = D.W;
+  if (n_workers != W || !status || !nproc || !n_long_running || !plen || !prefix || !count || !netocc || !nbytes ||
+      !idle || !saturated || !needs_ptr)
+    return fail(e, DGP_E_ARG, "dgp_audit_workers: one row per engine worker");
+  // dgp_sync_workers' normalisation, into what it would write
+  std::vector<int32_t> cap_(W), pf((size_t)W * dgp::PMAX, 0), pc((size_t)W * dgp::PMAX, 0), pl(W);
+  std::vector<uint8_t> fl(W);
+  std::vector<int64_t> slots(W, 0), nptr(W + 1, 0);
+  std::vector<uint32_t> ent;
+  int64_t tot[4] = {0, 0, 0, 0};  // idle, saturated, idle_task_count, its slots
+  RowAudit R;
+  const int RW = DGP_AR_ROW_WORKERS;
+  for (int w = 0; w < W; w++) {
+    if (status[w] < 0 || status[w] > 2) return fail(e, DGP_E_ARG, "dgp_audit_workers: status");
+    if (plen[w] < 0 || plen[w] > S::PD) return fail(e, DGP_E_ARG, "dgp_audit_workers: more than 8 prefixes on a worker");
+    const bool running = status[w] == 0;
+    if (!running && (idle[w] || saturated[w]))
+      return fail(e, DGP_E_ARG, "dgp_audit_workers: a worker that is not running is neither idle nor saturated");
+    if (status[w] != 2 && e->paused_h[w] == 2) return fail(e, DGP_E_ARG, "dgp_audit_workers: a removed worker returns");
+    if ((uint8_t)status[w] != e->paused_h[w])  // the host's copy of the status
+      R.host.push_back(dgp_violation{RW, DGP_AF_STATE, w, -1, e->paused_h[w], status[w]});
+    const int32_t nt = std::max<int32_t>(e->nthreads[w], 1);
+    const int32_t base = D.sat_inf ? 0 : std::max((int32_t)std::ceil(D.saturation * nt), (int32_t)1);
+    cap_[w] = base + (D.sat_inf ? 0 : n_long_running[w]);
+    pl[w] = plen[w];
+    for (int i = 0; i < plen[w]; i++) {
+      if (prefix[(size_t)w * S::PD + i] < 0 || prefix[(size_t)w * S::PD + i] >= D.P)
+        return fail(e, DGP_E_ARG, "dgp_audit_workers: prefix id");
+      pf[(size_t)w * dgp::PMAX + i] = prefix[(size_t)w * S::PD + i];
+      pc[(size_t)w * dgp::PMAX + i] = count[(size_t)w * S::PD + i];
+    }
+    const bool itc = running && (D.sat_inf || cap_[w] - nproc[w] > 0);
+    fl[w] = (uint8_t)((idle[w] ? dgp::WF_IDLE : 0) | (saturated[w] ? dgp::WF_SAT : 0) | (itc ? dgp::WF_ITC : 0) |
+                      (running ? 0 : dgp::WF_PAUSED));
+    slots[w] = itc && !D.sat_inf ? cap_[w] - nproc[w] : 0;
+    tot[0] += idle[w] ? 1 : 0;
+    tot[1] += saturated[w] ? 1 : 0;
+    tot[2] += itc ? 1 : 0;
+    tot[3] += slots[w];
+    const int64_t k0 = needs_ptr[w], k1 = needs_ptr[w + 1], m = k1 - k0;
+    if (k1 < k0 || (m > 0 && (!needs_task || !needs_count))) return fail(e, DGP_E_ARG, "dgp_audit_workers: needs_ptr");
+    if (m > (S::NLW - 1) + S::NXW) {  // scan mode: the entries are not compared; the kernel skips on the length
+      nptr[w + 1] = nptr[w] + m;
+      ent.resize(ent.size() + (size_t)m, 0u);
+      continue;
+    }
+    for (int64_t k = 0; k < m; k++) {
+      const int32_t d = needs_task[k0 + k], c = needs_count[k0 + k];
+      if (d < 0 || d >= D.N || c <= 0 || c > 255) return fail(e, DGP_E_ARG, "dgp_audit_workers: needs_what entry");
+      ent.push_back(((uint32_t)d << 8) | (uint32_t)c);
+    }
+    nptr[w + 1] = nptr[w] + m;
+  }
+  if (!D.sat_inf) R.cmp(D.w_cap, cap_.data(), W, 4, RW, DGP_AF_CAP);
+  R.cmp(D.w_nproc, nproc, W, 4, RW, DGP_AF_NPROC);
+  R.cmp(D.w_plen, pl.data(), W, 4, RW, DGP_AF_DICT_LEN);
+  const size_t lim = R.put(pl.data(), (size_t)W * 4);
+  R.cmp(D.w_pfx, pf.data(), (long long)W * dgp::PMAX, 4, RW, DGP_AF_DICT_PREFIX, RowAudit::NONE, dgp::PMAX, ~0ull, -1, D.w_plen, lim);
+  R.cmp(D.w_pcnt, pc.data(), (long long)W * dgp::PMAX, 4, RW, DGP_AF_DICT_COUNT, RowAudit::NONE, dgp::PMAX, ~0ull, -1, D.w_plen, lim);
+  R.cmp(D.w_netocc, netocc, W, 8, RW, DGP_AF_NETOCC);
+  R.cmp(D.w_nbytes, nbytes, W, 8, RW, DGP_AF_NBYTES);
+  R.cmp(D.w_flags, fl.data(), W, 1, RW, DGP_AF_FLAGS);
+  if (!D.sat_inf) R.cmp(D.w_itcslots, slots.data(), W, 8, RW, DGP_AF_ITCSLOTS);
+  const char* c = (const char*)e->ctl;
+  R.cmp(c + offsetof(dgp::Ctl, n_idle), &tot[0], 1, 8, RW, DGP_AF_N_IDLE);
+  R.cmp(c + offsetof(dgp::Ctl, n_sat), &tot[1], 1, 8, RW, DGP_AF_N_SAT);
+  R.cmp(c + offsetof(dgp::Ctl, n_itc), &tot[2], 1, 8, RW, DGP_AF_N_ITC);
+  if (!D.sat_inf) R.cmp(c + offsetof(dgp::Ctl, itc_slots), &tot[3], 1, 8, RW, DGP_AF_ITC_SLOTS);
+  if (ent.empty()) ent.push_back(0u);
+  R.jobs.push_back(RowAudit::Job{2, nullptr, R.put(nptr.data(), nptr.size() * 8), R.put(ent.data(), ent.size() * 4),
+                                 RowAudit::NONE, W, 1, 4, RW, DGP_AF_NEEDS_COUNT, -1, ~0ull, nullptr});
+  return row_audit_run(e, R, cap, out, n_violations);
+}
+
+int dgp_audit_globals(dgp_engine* e, int64_t n_tasks_counter, double network_occ_global, int32_t g_plen,
+                      const int32_t* g_prefix, const int64_t* g_count, int64_t n_queued, const int32_t* queued,
+                      const double* duration_average, const double* max_exec_time, double bandwidth,
+                      const int64_t* group_released_waiting, const int64_t* group_left,
+                      const int32_t* group_last_worker, int64_t cap, dgp_violation* out, int64_t* n_violations) {
+  if (int rc_ = resident_stop(e)) return rc_;
+  if (int rc = row_audit_ready(e, "dgp_audit_globals", cap, out, n_violations)) return rc;
+  const dgp::Dev& D = e->D;
+  if (g_plen < 0 || g_plen > dgp::PMAX_G || (g_plen > 0 && (!g_prefix || !g_count)) || n_queued < 0 ||
+      n_queued > D.N || (n_queued > 0 && !queued) || !duration_average || !max_exec_time || !(bandwidth > 0) ||
+      !group_released_waiting || !group_left || !group_last_worker)
+    return fail(e, DGP_E_ARG, "dgp_audit_globals: bad arguments");
+  for (int i = 0; i < g_plen; i++)
+    if (g_prefix[i] < 0 || g_prefix[i] >= D.P) return fail(e, DGP_E_ARG, "dgp_audit_globals: prefix id");
+  for (int64_t i = 0; i < n_queued; i++)
+    if (queued[i] < 0 || queued[i] >= D.N) return fail(e, DGP_E_ARG, "dgp_audit_globals: queued task");
+  for (int g = 0; g < D.G; g++)
+    if (group_last_worker[g] < -1 || group_last_worker[g] >= D.W) return fail(e, DGP_E_ARG, "dgp_audit_globals: last worker");
+  RowAudit R;
+  const int RG = DGP_AR_ROW_GLOBALS;
+  const char* c = (const char*)e->ctl;
+  const int64_t nocc = dbits(network_occ_global);
+  R.cmp(c + offsetof(dgp::Ctl, n_tasks), &n_tasks_counter, 1, 8, RG, DGP_AF_N_TASKS);
+  R.cmp(c + offsetof(dgp::Ctl, g_netocc), &nocc, 1, 8, RG, DGP_AF_G_NETOCC);
+  R.cmp(c + offsetof(dgp::Ctl, g_plen), &g_plen, 1, 4, RG, DGP_AF_DICT_LEN);
+  R.cmp(c + offsetof(dgp::Ctl, g_pfx), g_prefix, g_plen, 4, RG, DGP_AF_DICT_PREFIX);  // the ordered sequence
+  R.cmp(c + offsetof(dgp::Ctl, g_pcnt), g_count, g_plen, 8, RG, DGP_AF_DICT_COUNT);
+  static const int32_t none = 0;
+  R.jobs.push_back(RowAudit::Job{1, nullptr, R.put(n_queued ? queued : &none, (size_t)std::max<int64_t>(n_queued, 1) * 4),
+                                 RowAudit::NONE, RowAudit::NONE, n_queued, 1, 4, RG, DGP_AF_QUEUE_ENTRY, -1, ~0ull, nullptr});
+  int k = 0;
+  for (const double* p : {D.pdur_cur, D.pdur_walk, D.pdur_pre}) R.cmp(p, duration_average, D.P, 8, RG, DGP_AF_DURATION, RowAudit::NONE, 1, ~0ull, k++);
+  R.cmp(D.pmaxexec, max_exec_time, D.P, 8, RG, DGP_AF_MAX_EXEC);
+  R.cmp(D.g_relwait, group_released_waiting, D.G, 8, RG, DGP_AF_RELWAIT);
+  R.cmp(D.g_left, group_left, D.G, 8, RG, DGP_AF_GROUP_LEFT);
+  R.cmp(D.g_lastw, group_last_worker, D.G, 4, RG, DGP_AF_GROUP_LASTW);
+  if (dbits(D.bandwidth) != dbits(bandwidth))  // a host-side Dev field
+    R.host.push_back(dgp_violation{RG, DGP_AF_BANDWIDTH, -1, -1, dbits(D.bandwidth), dbits(bandwidth)});
+  return row_audit_run(e, R, cap, out, n_violations);
 }
 
 int dgp_snapshot(dgp_engine* e) {

@@ -6,6 +6,7 @@ keeps the graph resident in HBM and replays the reference placement path on the 
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 
@@ -28,7 +29,35 @@ DEFAULT_CONFIG = {  # distributed/distributed.yaml:13,16,24,28
 # ids of dgp_kernel_times; id 2 is the persistent replay kernel (k_stream; k_replay when P > PD);
 # 4..6 are WorkStealing (levels + bins, thief argmin, balance walk)
 KERNEL_NAMES = ("frontier_release", "candidate_commbytes", "replay", "update_graph", "steal_levels",
-                "steal_thief_argmin", "steal_balance", "unused")
+                "steal_thief_argmin", "steal_balance", "audit")  # 7: the five kernels of dgp_audit_state
+
+
+# ids of include/dgplace.h's dgp_audit_rule / dgp_audit_field
+AUDIT_RULES = {1: "TASK_PROC", 2: "TASK_HOLDERS", 3: "TASK_REMAINING", 4: "TASK_WAITERS", 5: "WORKER_NPROC",
+               6: "WORKER_DICT", 7: "GLOBAL_DICT", 8: "WORKER_NBYTES", 9: "WORKER_NEEDS", 10: "WORKER_FLAGS",
+               11: "QUEUE", 12: "GROUP_COUNT", 13: "ROW_TASKS", 14: "ROW_WORKERS", 15: "ROW_GLOBALS"}
+AUDIT_FIELDS = {1: "proc_on", 2: "holders", 3: "holder_of", 4: "multi", 5: "remaining", 6: "waiters", 7: "nproc",
+                8: "cap", 9: "dict_len", 10: "dict_prefix", 11: "dict_count", 12: "nbytes", 13: "needs_len",
+                14: "needs_task", 15: "needs_count", 16: "netocc", 17: "flags", 18: "itcslots", 19: "n_idle",
+                20: "n_sat", 21: "n_itc", 22: "itc_slots", 23: "queue_range", 24: "queue_entry", 25: "queue_member",
+                26: "relwait", 27: "state", 28: "res_nbytes", 29: "cur_nbytes", 30: "lr", 31: "wanted", 32: "forgotten",
+                33: "who_has", 34: "nthreads", 35: "n_tasks", 36: "g_netocc", 37: "queue_len", 38: "duration",
+                39: "max_exec", 40: "bandwidth", 41: "group_left", 42: "group_lastw"}
+AUDIT_FLOAT_FIELDS = frozenset((36, 38, 39, 40))  # doubles, stored as their bits
+
+# one record of dgp_audit_state: rule / field by name, index = task, worker, group or queue
+# position, sub = prefix, dependency or slot (-1: none), the engine's value and the recount's
+Violation = collections.namedtuple("Violation", "rule field index sub device_value expected_value")
+
+
+class _CViolation(C.Structure):  # struct dgp_violation
+    _fields_ = [("rule", C.c_int32), ("field", C.c_int32), ("index", C.c_int64), ("sub", C.c_int64),
+                ("device_value", C.c_int64), ("expected_value", C.c_int64)]
+
+
+class ViolationList(list):
+    """The records an audit kept; ``total`` counts every violation found (>= len)."""
+    total = 0
 
 
 def conflict_depth(g: dict, out: dict, first: int = 0) -> tuple[int, int]:
@@ -613,6 +642,79 @@ class PlacementEngine:
             self.sync_workers(workers)
         if globals_ is not None:
             self.sync_globals(globals_)
+
+    def audit_state(self, cap: int = 64):
+        """``dgp_audit_state``: the engine's resident state recounted on the device and checked
+        against itself (rules in include/dgplace.h). Read-only. Returns ``(violations,
+        n_skipped)``: up to ``cap`` ``Violation`` records sorted by (rule, field, index, sub),
+        and the number of workers whose needs_what is in scan mode (not compared).
+        ``violations.total`` is the number found, which may exceed ``cap``."""
+        cap = int(cap)
+        buf = (_CViolation * max(cap, 1))()
+        n, sk = C.c_int64(0), C.c_int64(0)
+        rc = self.lib.dgp_audit_state(self.h, cap, C.cast(buf, C.c_void_p), C.byref(n), C.byref(sk))
+        if rc != 0:
+            msg = self.lib.dgp_last_error(self.h)
+            raise _lib.DgpError(f"dgp_audit_state failed ({rc}): {msg.decode() if msg else ''}")
+        out = ViolationList(
+            Violation(AUDIT_RULES.get(v.rule, v.rule), AUDIT_FIELDS.get(v.field, v.field), int(v.index), int(v.sub),
+                      int(v.device_value), int(v.expected_value))  # every self-audit field is an integer
+            for v in buf[:min(int(n.value), cap)])
+        out.total = int(n.value)
+        return out, int(sk.value)
+
+    def _violations(self, buf, n, cap):
+        def val(f, v):
+            return float(np.array([v], np.int64).view(np.float64)[0]) if f in AUDIT_FLOAT_FIELDS else int(v)
+
+        out = ViolationList(
+            Violation(AUDIT_RULES.get(v.rule, v.rule), AUDIT_FIELDS.get(v.field, v.field), int(v.index), int(v.sub),
+                      val(v.field, v.device_value), val(v.field, v.expected_value)) for v in buf[:min(n, cap)])
+        out.total = n
+        return out
+
+    def audit_rows(self, tasks=None, workers=None, globals_=None, cap: int = 64):
+        """``dgp_audit_tasks`` / ``_workers`` / ``_globals``: a dry run of ``sync`` with the same
+        row dicts (``sync.task_rows`` / ``worker_rows`` / ``global_rows``). Read-only. Returns the
+        ``Violation`` records (rules ROW_TASKS / ROW_WORKERS / ROW_GLOBALS): every field the
+        engine holds that the resync, given these rows, would change -- empty when the device's
+        state is the scheduler's. Up to ``cap`` records per row kind; ``.total`` counts all."""
+        cap = int(cap)
+        found = ViolationList()
+        calls = []
+        if tasks is not None:
+            k = ("task", "state", "remaining", "waiters", "processing_on", "nbytes", "long_running", "wanted",
+                 "holder_ptr", "holder_idx")
+            dts = (np.int32, np.uint8, np.int32, np.int32, np.int32, np.int64, np.uint8, np.uint8, np.int64, np.int32)
+            a = [self._arr(tasks[n], d) for n, d in zip(k, dts)]
+            calls.append(("dgp_audit_tasks", (len(a[0]), *[_ptr(x) for x in a]), a))
+        if workers is not None:
+            k = ("status", "nproc", "n_long_running", "plen", "prefix", "count", "netocc", "nbytes", "idle",
+                 "saturated", "needs_ptr", "needs_task", "needs_count")
+            dts = (np.int8, np.int32, np.int32, np.int32, np.int32, np.int32, np.int64, np.int64, np.uint8, np.uint8,
+                   np.int64, np.int32, np.int32)
+            a = [self._arr(workers[n], d) for n, d in zip(k, dts)]
+            calls.append(("dgp_audit_workers", (len(a[0]), *[_ptr(x) for x in a]), a))
+        if globals_ is not None:
+            g = globals_
+            a = [self._arr(g["g_prefix"], np.int32), self._arr(g["g_count"], np.int64), self._arr(g["queued"], np.int32),
+                 self._arr(g["duration_average"], np.float64), self._arr(g["max_exec_time"], np.float64),
+                 self._arr(g["group_released_waiting"], np.int64), self._arr(g["group_left"], np.int64),
+                 self._arr(g["group_last_worker"], np.int32)]
+            calls.append(("dgp_audit_globals", (int(g["n_tasks"]), float(g["network_occ_global"]), len(a[0]), _ptr(a[0]),
+                                                _ptr(a[1]), len(a[2]), _ptr(a[2]), _ptr(a[3]), _ptr(a[4]),
+                                                float(g["bandwidth"]), _ptr(a[5]), _ptr(a[6]), _ptr(a[7])), a))
+        for name, args, _keep in calls:
+            buf = (_CViolation * max(cap, 1))()
+            n = C.c_int64(0)
+            rc = getattr(self.lib, name)(self.h, *args, cap, C.cast(buf, C.c_void_p), C.byref(n))
+            if rc != 0:
+                msg = self.lib.dgp_last_error(self.h)
+                raise _lib.DgpError(f"{name} failed ({rc}): {msg.decode() if msg else ''}")
+            part = self._violations(buf, int(n.value), cap)
+            found.extend(part)
+            found.total += part.total
+        return found
 
     def snapshot(self):
         """Append one per-worker snapshot (service mode round boundary)."""

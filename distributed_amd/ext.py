@@ -52,6 +52,7 @@ import functools
 import inspect
 import logging
 import math
+import time
 from collections import Counter, deque
 from itertools import chain, islice, repeat
 from operator import attrgetter, lt, truth
@@ -318,12 +319,24 @@ class GPUPlacementExtension(SchedulerPlugin):
     """Scheduler extension that takes placement decisions from the HIP engine."""
 
     name = "gpu-placement"
+    # the state audit's knobs and marks (instances built without __init__ read these)
+    validate = False
+    audit_interval = 0.0
+    _last_audit = 0.0
+    _audit_logged = False
+    _posted = None
 
-    def __init__(self, scheduler, *, device: int = 0, engine_factory=None, validate: bool = False):
+    def __init__(self, scheduler, *, device: int = 0, engine_factory=None, validate: bool = False,
+                 audit_interval: float = 0):
         self.scheduler = scheduler
         self.device = device
         self.engine_factory = engine_factory
         self.validate = validate
+        # seconds between self-audits of the engine's state on a live scheduler (0: off), taken
+        # at the start of the first stimulus after the interval ran out
+        self.audit_interval = float(audit_interval or 0)
+        self._last_audit = time.monotonic()
+        self._audit_logged = False
         self.engine = None
         self.active = True
         self.reason = None        # why the extension fell back to the reference decisions
@@ -621,6 +634,8 @@ class GPUPlacementExtension(SchedulerPlugin):
         self._losing = address
         self.stats["workers_lost_on_device"] += 1
         self._fetch(n)
+        if self.validate:
+            self._audit_validate(f"remove_worker({address})")
         return True
 
     def _wrap_replicas(self):
@@ -801,6 +816,8 @@ class GPUPlacementExtension(SchedulerPlugin):
             return None
         self.stats[what] += 1
         self._fetch()  # a refill the operation made (resume, long-running)
+        if self.validate and r is not None and what in ("release_tasks", "reschedule"):
+            self._audit_validate(what)
         return r
 
     def _wrap_stealing(self):
@@ -902,12 +919,70 @@ class GPUPlacementExtension(SchedulerPlugin):
         self.reason = reason
         self.pending.clear()
 
+    def audit(self, full: bool = False):
+        """The engine's resident state checked on the device (``PlacementEngine.audit_state``:
+        every aggregate recounted from the per-task arrays, rules in include/dgplace.h).
+        ``full``: also every engine task's row and the worker and global rows, read from the
+        scheduler as for a resync (``distributed_amd/sync.py``), against the engine's state
+        (``audit_rows``: a dry run of the resync). Returns the violations (empty: consistent
+        and, with ``full``, equal to the scheduler's). An engine without the methods (the round
+        engine's stand-ins, test doubles) is skipped. A non-empty result is logged once, with
+        its first records."""
+        fn = getattr(self.engine, "audit_state", None)
+        if fn is None or not self.active or self.suspended or self._posted is not None:
+            return []
+        found, _skipped = fn()
+        rows = getattr(self.engine, "audit_rows", None) if full else None
+        if rows is not None:
+            s = self.scheduler
+            widx = {a: i for i, a in enumerate(self.workers)}
+            pnames = sorted(self.prefix_index, key=self.prefix_index.get)
+            gnames = sorted(self.group_index, key=self.group_index.get)
+            more = rows(sync.task_rows(s, self.keys, self.task_index, widx),
+                        sync.worker_rows(s, self.workers, self.prefix_index, self.task_index),
+                        sync.global_rows(s, pnames, self.prefix_dur, gnames, self.task_index, widx))
+            total = getattr(found, "total", len(found)) + getattr(more, "total", len(more))
+            found = type(found)(list(found) + list(more)) if isinstance(found, list) else list(found) + list(more)
+            try:
+                found.total = total
+            except AttributeError:
+                pass
+        if found and not self._audit_logged:
+            self._audit_logged = True
+            logger.warning("gpu-placement: the engine's state is inconsistent (%d violations): %s",
+                           getattr(found, "total", len(found)), list(found[:4]))
+        return found
+
+    def _audit_validate(self, what: str):
+        """validate=True: the self-audit after a stimulus the engine followed on its own
+        (a release, a reschedule, a worker loss) and after every resync."""
+        found = self.audit()
+        assert not found, f"gpu-placement: engine state after {what}: {list(found[:4])}"
+
+    def _audit_due(self):
+        """The ``audit-interval`` knob: a self-audit once the interval ran out; a violation
+        hands placement back to the scheduler with the first record as the reason."""
+        now = time.monotonic()
+        if now - self._last_audit < self.audit_interval:
+            return
+        self._last_audit = now
+        try:
+            found = self.audit()
+        except Exception as e:
+            self.fallback(f"state audit: {e}")
+            return
+        self.stats["audits"] += 1
+        if found:
+            self.fallback(f"state audit: {found[0]}")
+
     def _enter(self):
         """A new stimulus starts: the previous one's window closes and, if the scheduler
         decided it itself, the engine takes the scheduler's state first."""
         self._close_window()
         if self.suspended:
             self._resync()
+        if self.audit_interval > 0 and self.active and self.engine is not None:
+            self._audit_due()
 
     def _suspend(self, reason: str):
         """The running stimulus is the scheduler's own (a change the engine does not model):
@@ -971,6 +1046,8 @@ class GPUPlacementExtension(SchedulerPlugin):
         self._dirty = set()
         self._dirty_all = False
         self.pending.clear()
+        if self.validate and self.active:
+            self._audit_validate("a resync")
 
     def _config(self):
         from distributed import scheduler as sched_mod

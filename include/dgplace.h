@@ -70,7 +70,7 @@
 extern "C" {
 #endif
 
-#define DGP_ABI_VERSION 21
+#define DGP_ABI_VERSION 22
 
 #define DGP_OK 0
 #define DGP_E_ARG -1     /* invalid argument / shape */
@@ -306,7 +306,8 @@ int dgp_graph_stimulus(dgp_engine* e, int64_t* n_new_placements);
  * processing -> released (it leaves its worker); waiting / queued / no-worker -> released
  * (waiting_on, queued, unrunnable); a cancelled task leaves its dependencies' waiters.
  * who_wants emptied; forget[i] != 0: forgotten (the row stays, released, out of every
- * dependents walk). Then the queue refill (:5430). *n_new_placements: its placements.
+ * dependents walk and out of its TaskGroup's states["released"], ABI 22). Each task is listed
+ * once. Then the queue refill (:5430). *n_new_placements: its placements.
  * DGP_E_UNSUPPORTED with nothing changed for an erred or forgotten task (the scheduler
  * decides, then dgp_sync_*). */
 int dgp_release_tasks(dgp_engine* e, int64_t n, const int32_t* task, const uint8_t* forget, int64_t* n_new_placements);
@@ -474,6 +475,211 @@ int dgp_sync_globals(dgp_engine* e, int64_t n_tasks_counter, double network_occ_
                      const int32_t* g_prefix, const int64_t* g_count, int64_t n_queued, const int32_t* queued,
                      const double* duration_average, const double* max_exec_time, double bandwidth,
                      const int64_t* group_released_waiting, const int64_t* group_left, const int32_t* group_last_worker);
+
+/* ---- State audit (ABI 22). dgp_audit_state is a read-only check of the engine's resident
+ * state against itself: grid-wide kernels recount every aggregate from the per-task arrays
+ * and report where the kept value disagrees. No device field of the engine's state and no
+ * host field that describes it changes (mode, evf, pending_resync and the host flag copies
+ * included); what the call does touch is its own scratch arena and, as every entry point,
+ * the published copy of the Dev block (the debug knobs read from the environment, the
+ * derived needs_stream). The host cost is O(W): the workers' base caps and status bytes are
+ * uploaded per call. The resident kernel is ended first, like every entry point but
+ * dgp_tasks_finished. The rules restate
+ * Scheduler.validate_state (scheduler.py:5544-5630) and validate_task_state (:8596-8746) in
+ * the engine's canonical HBM layout, the one the stream kernel writes back when it exits:
+ *
+ *   DGP_AR_TASK_PROC       proc_on >= 0 iff the state is processing (:8646); the worker of a
+ *                          processing task is a worker and not a removed one (:5477-5482)
+ *   DGP_AR_TASK_HOLDERS    the who_has row (holders[t][WB]) is non-empty iff the state is memory
+ *                          (:8647); no bit at or beyond W, none on a removed worker (:8708-8716);
+ *                          more than one bit implies TD_MULTI; holder_of names a holder of a task
+ *                          in memory (the stream kernel reads who_has as holder_of without
+ *                          TD_MULTI). TD_MULTI with one bit or none is the engine's state after a
+ *                          replica was removed again or the stream kernel released the result:
+ *                          the flag only selects the row over holder_of, and the two agree
+ *                          holder_of of a row without holders is not compared (the stream kernel
+ *                          leaves the last holder there when it releases a result): every
+ *                          holds_any call is on a dependency of a task that is processing or
+ *                          being placed, all in memory, or follows a state == memory test
+ *                          (`grep -n "holds_any" csrc/`)
+ *   DGP_AR_TASK_REMAINING  waiting: remaining == number of dependencies with an empty who_has
+ *                          row, and > 0 (:5452-5460, :8649-8664); queued / processing /
+ *                          no-worker: every dependency is held and remaining == 0. Not compared
+ *                          in the other states: released / erred / memory rows keep what the
+ *                          stream builder counted down (dgp_events.h ERRED_REMAINING), and
+ *                          nothing reads remaining there before a transition sets it
+ *   DGP_AR_TASK_WAITERS    a task in memory: waiters == number of its dependents that are
+ *                          waiting / queued / processing / no-worker (:5497-5500); forgotten
+ *                          rows (TF_FORGOTTEN) are not counted
+ *   DGP_AR_WORKER_NPROC    w_nproc[w] == number of tasks with proc_on == w (:5580); w_cap[w] ==
+ *                          max(ceil(saturation * max(nthreads, 1)), 1) + number of those with
+ *                          TD_LR (:8762-8767, the cap rule of dgp_sync_workers). With
+ *                          worker-saturation inf w_cap is not compared: no kernel decides by
+ *                          it there (worker_full and the slot tests check sat_inf first, the
+ *                          rest is `sat_inf ? 0 : w_cap`; `grep -n "w_cap\[\|cap\[" csrc/`) and
+ *                          its writers disagree (k_ev_long_running adds 1, the resync writes 0)
+ *   DGP_AR_WORKER_DICT     per worker: 0 <= w_plen <= 8, the dict's prefixes are distinct and in
+ *                          range and its counts > 0; each count == number of tasks processing on
+ *                          w with that prefix and without TD_LR; no other prefix processes
+ *                          there (:747-784)
+ *   DGP_AR_GLOBAL_DICT     Ctl.g_plen / g_pfx / g_pcnt: distinct prefixes, and key set and
+ *                          counts equal the sums over the workers' dicts (:5596-5600)
+ *   DGP_AR_WORKER_NBYTES   w_nbytes[w] == sum of get_nbytes over tasks whose who_has row has
+ *                          bit w (:5622-5627)
+ *   DGP_AR_WORKER_NEEDS    a worker whose needs_what table is in line or overflow form: the
+ *                          entries name distinct tasks in range with counts > 0, the control
+ *                          word's entry count is the number of entries, and the (task, count)
+ *                          multiset equals, over tasks processing on w, the dependencies w does
+ *                          not hold, with multiplicity (:5585-5591); w_netocc[w] == sum of
+ *                          get_nbytes over the entries (:800-830). A worker in scan mode is
+ *                          counted in *n_skipped and not compared. Once the engine has seen a
+ *                          replica event or a resync (EVF_MULTI) the multiset is an upper
+ *                          bound only: add_replica deletes an entry whatever its count
+ *                          (:831-834) and remove_replica does not restore it (:786-798), in the
+ *                          reference as here, and needs_dec accepts the missing entry under
+ *                          exactly that flag; an entry that counts more tasks than need it,
+ *                          or names a dependency the worker holds, is still a violation
+ *   DGP_AR_WORKER_FLAGS    a worker that is not running is neither idle, saturated nor in
+ *                          idle_task_count; idle and saturated are disjoint; a running worker
+ *                          with nproc == 0 is idle; the idle_task_count flag and w_itcslots
+ *                          follow dgp_sync_workers' rule (running and (inf or cap - nproc > 0);
+ *                          cap - nproc, 0 under inf); Ctl.n_idle / n_sat / n_itc / itc_slots
+ *                          equal the popcounts and the sum (:5550-5584). With worker-saturation
+ *                          inf w_itcslots and Ctl.itc_slots are not compared: their one reader
+ *                          is the queue refill, which returns on an empty queue first and
+ *                          nothing queues under inf (`grep -n "itc_slots\|itcslots" csrc/`:
+ *                          every other hit maintains them), and update_graph leaves
+ *                          cap - nproc < 0 there where the stream kernel and the resync write 0
+ *   DGP_AR_QUEUE           0 <= qhead, qlen and qhead + qlen <= N; qarr[qhead, qhead + qlen)
+ *                          holds exactly the tasks in state queued, each once, in ascending
+ *                          priority (:5464-5466)
+ *   DGP_AR_GROUP_COUNT     g_relwait[g] == number of the group's tasks released or waiting,
+ *                          forgotten ones not counted (sync.global_rows)
+ *
+ * Every index read from the state (proc_on, queue entries, needs task ids, prefix ids, dict
+ * lengths, holder_of) is range-checked before it is used: an out-of-range one is itself a
+ * violation and is never dereferenced.
+ *
+ * Availability: the stream engine (<= 32 prefixes), after dgp_update_graph and between service
+ * calls; DGP_E_STATE otherwise, while a resync is pending (the state is then the scheduler's to
+ * hand over), while a batch is posted, and on an engine advanced by dgp_run_rounds (a replay
+ * keeps per-round scratch in the same arrays; it is not canonical between rounds).
+ *
+ * Output: out[0 .. min(*n_violations, cap)) receives records sorted by (rule, field, index,
+ * sub); *n_violations is the total and may exceed cap (which records are kept is then
+ * unspecified). index: the task, worker, group or queue position; sub: the prefix, dependency
+ * or slot, or -1. Scratch for the recount belongs to the engine and grows with N, W and P. */
+enum dgp_audit_rule {
+  DGP_AR_TASK_PROC = 1,
+  DGP_AR_TASK_HOLDERS = 2,
+  DGP_AR_TASK_REMAINING = 3,
+  DGP_AR_TASK_WAITERS = 4,
+  DGP_AR_WORKER_NPROC = 5,
+  DGP_AR_WORKER_DICT = 6,
+  DGP_AR_GLOBAL_DICT = 7,
+  DGP_AR_WORKER_NBYTES = 8,
+  DGP_AR_WORKER_NEEDS = 9,
+  DGP_AR_WORKER_FLAGS = 10,
+  DGP_AR_QUEUE = 11,
+  DGP_AR_GROUP_COUNT = 12,
+  /* dgp_audit_tasks / _workers / _globals: a field the matching dgp_sync_* call would change */
+  DGP_AR_ROW_TASKS = 13,
+  DGP_AR_ROW_WORKERS = 14,
+  DGP_AR_ROW_GLOBALS = 15
+};
+enum dgp_audit_field {
+  DGP_AF_PROC_ON = 1,       /* proc_on[index] */
+  DGP_AF_HOLDERS = 2,       /* popcount of the who_has row; sub = an offending worker or -1 */
+  DGP_AF_HOLDER_OF = 3,     /* holder_of[index] */
+  DGP_AF_MULTI = 4,         /* TD_MULTI (0 / 1) */
+  DGP_AF_REMAINING = 5,     /* remaining[index] */
+  DGP_AF_WAITERS = 6,       /* waiters[index] */
+  DGP_AF_NPROC = 7,         /* w_nproc[index] */
+  DGP_AF_CAP = 8,           /* w_cap[index] */
+  DGP_AF_DICT_LEN = 9,      /* w_plen[index] / g_plen */
+  DGP_AF_DICT_PREFIX = 10,  /* a dict slot's prefix id; sub = slot */
+  DGP_AF_DICT_COUNT = 11,   /* a prefix's count in the dict (0: absent); sub = prefix */
+  DGP_AF_NBYTES = 12,       /* w_nbytes[index] */
+  DGP_AF_NEEDS_LEN = 13,    /* the control word's entry count */
+  DGP_AF_NEEDS_TASK = 14,   /* a needs_what slot's task id; sub = slot */
+  DGP_AF_NEEDS_COUNT = 15,  /* a dependency's count in needs_what (0: absent); sub = dependency */
+  DGP_AF_NETOCC = 16,       /* w_netocc[index] */
+  DGP_AF_FLAGS = 17,        /* w_flags[index] (WF_IDLE 1, WF_SAT 2, WF_ITC 4, WF_PAUSED 8) */
+  DGP_AF_ITCSLOTS = 18,     /* w_itcslots[index] */
+  DGP_AF_N_IDLE = 19,       /* Ctl.n_idle, n_sat, n_itc, itc_slots (index = -1) */
+  DGP_AF_N_SAT = 20,
+  DGP_AF_N_ITC = 21,
+  DGP_AF_ITC_SLOTS = 22,
+  DGP_AF_QUEUE_RANGE = 23,  /* qhead (sub 0) / qlen (sub 1) */
+  DGP_AF_QUEUE_ENTRY = 24,  /* qarr[qhead + index]: out of range, not queued, or out of order */
+  DGP_AF_QUEUE_MEMBER = 25, /* times task `index` is in the queue (expected: 1 iff queued) */
+  DGP_AF_RELWAIT = 26,      /* g_relwait[index] */
+  /* row audits only */
+  DGP_AF_STATE = 27,        /* state[index] */
+  DGP_AF_RES_NBYTES = 28,   /* res_nbytes[index] (TaskState.nbytes, raw) */
+  DGP_AF_CUR_NBYTES = 29,   /* cur_nbytes[index] (set_nbytes' value while in memory) */
+  DGP_AF_LR = 30,           /* TD_LR (0 / 1) */
+  DGP_AF_WANTED = 31,       /* TF_WANTED (0 / 1) */
+  DGP_AF_FORGOTTEN = 32,    /* TF_FORGOTTEN (0 / 1) */
+  DGP_AF_WHO_HAS = 33,      /* one 64-worker word of the who_has row; sub = word */
+  DGP_AF_NTHREADS = 34,     /* w_nthreads[index] */
+  DGP_AF_N_TASKS = 35,      /* Ctl.n_tasks */
+  DGP_AF_G_NETOCC = 36,     /* Ctl.g_netocc (double) */
+  DGP_AF_QUEUE_LEN = 37,    /* Ctl.qlen */
+  DGP_AF_DURATION = 38,     /* TaskPrefix.duration_average (double); index = prefix, sub 0 / 1 / 2 = the
+                               committed, walker's and prefetcher's copy */
+  DGP_AF_MAX_EXEC = 39,     /* TaskPrefix.max_exec_time (double); index = prefix */
+  DGP_AF_BANDWIDTH = 40,    /* SchedulerState.bandwidth (double) */
+  DGP_AF_GROUP_LEFT = 41,   /* g_left[index] */
+  DGP_AF_GROUP_LASTW = 42   /* g_lastw[index] */
+};
+typedef struct dgp_violation {
+  int32_t rule;   /* dgp_audit_rule */
+  int32_t field;  /* dgp_audit_field */
+  int64_t index;
+  int64_t sub;
+  int64_t device_value;    /* what the engine holds (doubles as their bits) */
+  int64_t expected_value;  /* what the recount gives */
+} dgp_violation;
+int dgp_audit_state(dgp_engine* e, int64_t cap, dgp_violation* out, int64_t* n_violations, int64_t* n_skipped);
+
+/* dgp_audit_tasks / _workers / _globals (ABI 22): a dry run of the resync. Arguments and
+ * argument checks are those of dgp_sync_tasks / _workers / _globals, plus the output of
+ * dgp_audit_state; nothing of the engine changes. A violation (rules DGP_AR_ROW_*) is a field
+ * the matching dgp_sync_* call, given these rows, would change: the rows are normalised on the
+ * host exactly as there (forgotten -> released + TF_FORGOTTEN, proc_on = -1 unless processing,
+ * cur_nbytes only for memory, cap / flags / slots from status, nproc and n_long_running) and
+ * compared on the device as the thing they represent: the who_has row as a set (bitset words),
+ * holder_of, TD_LR / TD_MULTI, needs_what as a multiset over line and overflow entries, the
+ * queue, the global dict and each worker's dict as ordered sequences (insertion order decides
+ * the fp64 occupancy sum). Doubles compare by bit pattern (device_value / expected_value hold
+ * the bits). index is the task, worker, prefix, group, dict slot or queue position; a scalar of
+ * the control block reads index 0, the host-side bandwidth index -1. fr_mark / rel_mark, which the resync merely resets, are not compared; a worker
+ * whose rows would send it to scan mode compares everything but its needs entries.
+ * Compared only where a kernel reads the field (the resync writes these unconditionally):
+ *   remaining       for waiting / queued / processing / no-worker rows (see DGP_AR_TASK_REMAINING)
+ *   holder_of       for processing rows and results with one holder (DGP_AR_TASK_HOLDERS; under
+ *                   TD_MULTI it names any holder and who_has is the row)
+ *   TD_MULTI        only "more than one holder implies the flag" (see DGP_AR_TASK_HOLDERS)
+ *   cur_nbytes      for rows in memory (get_nbytes is asked of held dependencies only; the
+ *                   stream kernel leaves the last value when it releases a result)
+ *   cap / slots     not under worker-saturation inf (see DGP_AR_WORKER_NPROC / _FLAGS)
+ * Availability as dgp_sync_* (stream engine; DGP_E_STATE otherwise and while a batch is
+ * posted), and DGP_E_STATE on an engine advanced by dgp_run_rounds. */
+int dgp_audit_tasks(dgp_engine* e, int64_t n, const int32_t* task, const uint8_t* state, const int32_t* remaining,
+                    const int32_t* waiters, const int32_t* processing_on, const int64_t* nbytes,
+                    const uint8_t* long_running, const uint8_t* wanted, const int64_t* holder_ptr,
+                    const int32_t* holder_idx, int64_t cap, dgp_violation* out, int64_t* n_violations);
+int dgp_audit_workers(dgp_engine* e, int32_t n_workers, const int8_t* status, const int32_t* nproc,
+                      const int32_t* n_long_running, const int32_t* plen, const int32_t* prefix, const int32_t* count,
+                      const int64_t* netocc, const int64_t* nbytes, const uint8_t* idle, const uint8_t* saturated,
+                      const int64_t* needs_ptr, const int32_t* needs_task, const int32_t* needs_count, int64_t cap,
+                      dgp_violation* out, int64_t* n_violations);
+int dgp_audit_globals(dgp_engine* e, int64_t n_tasks_counter, double network_occ_global, int32_t g_plen,
+                      const int32_t* g_prefix, const int64_t* g_count, int64_t n_queued, const int32_t* queued,
+                      const double* duration_average, const double* max_exec_time, double bandwidth,
+                      const int64_t* group_released_waiting, const int64_t* group_left,
+                      const int32_t* group_last_worker, int64_t cap, dgp_violation* out, int64_t* n_violations);
 
 /* Append one worker snapshot (needs dgp_enable_snapshots): round index = number of calls
  * (update_graph's snapshot is round 0). */
