@@ -264,13 +264,21 @@ __device__ __forceinline__ unsigned long long mclk() { return DGP_PROF ? __built
 // wait, 12 after the wait, 13 first frontier keys, 14 argmin + early release, 15 first commit,
 // 16 frontier done, 17 refill done, 18 w released, 19 the stimulus whose release made it
 // ready, 20 candidates final (predc 0), 21 the stimulus whose release did that,
-// 22 nf | kt << 8 | nrel << 16 | nt << 24, 23 predc at the claim. One row is DGP_TSTR words.
+// 22 nf | kt << 8 | nrel << 16 | nt << 24, 23 predc at the claim.
+// DGP_TRACE=4: those, plus stamps inside the three largest phases: 24 the completion's needs
+// decrements, 25 w's needs line stored, 26 w's dict updated (the rest up to 10 is the network
+// term); 27 the argmin's key loop (the rest up to 14 is the early release); in the first commit
+// 28 placement stored + the chosen worker's needs line loaded, 29 needs increments, 30 line
+// stored + dict updated, 31 network term + error ballot (the rest up to 15 is the occupancy
+// and the record). Every stamp drains the wave's LDS counter: the sub-phases read a little
+// longer than they run unstamped. One row is TSTR words.
 #ifndef DGP_TRACE
 #define DGP_TRACE 0
 #endif
 constexpr int TSTR = 32;
-constexpr bool TRL = DGP_TRACE == 1 || DGP_TRACE == 3;  // lifecycle events
-constexpr bool TR3 = DGP_TRACE == 3;                     // executor phases
+constexpr bool TRL = DGP_TRACE == 1 || DGP_TRACE >= 3;  // lifecycle events
+constexpr bool TR3 = DGP_TRACE >= 3;                     // executor phases
+constexpr bool TR4 = DGP_TRACE == 4;                     // stamps inside the executor's phases
 __device__ __forceinline__ void trace_at(const Dev& D, long long r, int k, unsigned long long v) {
   if (DGP_TRACE && D.trace && r >= D.trace_lo && r < D.trace_lo + D.trace_n) D.trace[(r - D.trace_lo) * TSTR + k] = v;
 }
@@ -466,6 +474,44 @@ __device__ __forceinline__ void wd_set(WDict& d, int p, uint32_t v) {
 
 // add_to_processing (+1) / remove_from_processing (-1) of one task of prefix p
 __device__ __forceinline__ bool dict_add(WDict& d, int p, int delta) {
+  // dicts of at most two entries in every active lane (the common case: a worker runs one or
+  // two prefixes at a time; the executors update one lane's dict): slots 0 and 1 compared
+  // directly, without the search over the eight slots and the per-lane selection of a slot by
+  // index (a branch tree per wd_slot / wd_put). The same updates as the general form below.
+  if (!ballot(wd_n(d.ord) > 2u)) {
+    const uint32_t n2 = wd_n(d.ord);
+    const bool m1 = n2 > 1u && (d.c.y >> 24) == (uint32_t)p;
+    const bool m0 = !m1 && n2 > 0u && (d.c.x >> 24) == (uint32_t)p;  // (wd_find: the last match)
+    if (delta > 0) {
+      const uint32_t v = m0 ? d.c.x : d.c.y;
+      const bool hit = m0 || m1;
+      const bool full = hit && (v & 0xffffffu) == 0xffffffu;
+      const bool app = !hit && p >= 0 && p <= 255;  // new key: appended at slot n2 <= 2
+      const uint32_t fresh = ((uint32_t)p << 24) | 1u;
+      d.c.x = (m0 && !full) ? d.c.x + 1u : ((app && n2 == 0u) ? fresh : d.c.x);
+      d.c.y = (m1 && !full) ? d.c.y + 1u : ((app && n2 == 1u) ? fresh : d.c.y);
+      d.c.z = (app && n2 == 2u) ? fresh : d.c.z;
+      d.ord = app ? d.ord + (1u << 24) : d.ord;
+      return hit ? !full : app;
+    }
+    const uint32_t v = m0 ? d.c.x : d.c.y;
+    const bool dec = (m0 || m1) && (v & 0xffffffu) > 1u;
+    const bool g0 = m0 && !dec, g1 = (m0 || m1) && !dec;  // the key leaves: slots from it on move up
+    if (ballot(g1)) {
+      d.c.x = g0 ? d.c.y : d.c.x;
+      d.c.y = g1 ? d.c.z : d.c.y;
+      d.c.z = g1 ? d.c.w : d.c.z;
+      d.c.w = g1 ? d.c1.x : d.c.w;
+      d.c1.x = g1 ? d.c1.y : d.c1.x;
+      d.c1.y = g1 ? d.c1.z : d.c1.y;
+      d.c1.z = g1 ? d.c1.w : d.c1.z;
+      d.c1.w = g1 ? 0u : d.c1.w;
+      d.ord = g1 ? d.ord - (1u << 24) : d.ord;
+    }
+    d.c.x = (m0 && dec) ? d.c.x - 1u : d.c.x;
+    d.c.y = (m1 && dec) ? d.c.y - 1u : d.c.y;
+    return true;
+  }
   const int k = wd_find(d, p);
   const uint32_t n = wd_n(d.ord);
   if (delta > 0) {
@@ -2423,14 +2469,6 @@ __device__ __forceinline__ bool key_less(const Key& a, const Key& b) {
   if (a.nb != b.nb) return a.nb < b.nb;
   return a.w < b.w;
 }
-__device__ __forceinline__ Key key_at(const Key& k, int l) {
-  Key o;
-  o.start = mkd(rlu(dlo(k.start), l), rlu(dhi(k.start), l));
-  o.nb = mk64(rlu(lo32(k.nb), l), rlu(hi32(k.nb), l));
-  o.w = rl(k.w, l);
-  o.comm = mk64(rlu(lo32(k.comm), l), rlu(hi32(k.comm), l));
-  return o;
-}
 
 // start time as a u64 whose unsigned order is key_less's fp64 order (+0 and -0 equal)
 __device__ __forceinline__ uint64_t start_key(double x) {
@@ -2535,7 +2573,6 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
   }
   const int jw = __builtin_ctzll(wm);
   const bool isw = lane == jw;
-  double nbw = net_bw_of(net, D);            // this lane's netocc / bandwidth
   const bool nth1 = !ballot(tl && nth != 1);  // occ / 1.0 == occ: the division is skipped
   phase(16);
   if (DGP_TRACE == 2 && lane == 0) TR(r, 1);
@@ -2556,15 +2593,19 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
     const int64_t nb = mk64(rlu(E.z, L_), rlu(E.w, L_));
     dnet -= needs_dec(D, S, w, nl, d, nb, t);
   }
+  if (TR4 && lane == 0) TR(r, 24);
   const int npw = rl(np, jw) - 1;
   if (npw == 0) needs_reset(D, w, nl);
   line_store<LW>(P, w, nl);
+  if (TR4 && lane == 0) TR(r, 25);
   if (isw) {
     dict_add(dj, p, -1);
     np = npw;
     net += dnet;
   }
-  if (dnet != 0) nbw = net_bw_of(net, D);  // dnet is uniform
+  if (TR4 && lane == 0) TR(r, 26);
+  // this lane's netocc / bandwidth: one division, once the completion's change is in
+  double nbw = net_bw_of(net, D);
   phase(17);
   if (DGP_TRACE == 2 && lane == 0) TR(r, 3);
   if (TR3 && lane == 0) TR(r, 10);
@@ -2668,16 +2709,30 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
       serr(S, SERR_CAND, x);
       return true;
     }
-    Key best = key_at(k, __builtin_ctzll(cm));
+    // key_less over the candidates, reading only what it compares: every candidate's start,
+    // nbytes and the worker index only of two that tie on start, the rest of the winner alone
     int jb = __builtin_ctzll(cm);
+    Key best;
+    double bs = mkd(rlu(dlo(k.start), jb), rlu(dhi(k.start), jb));
     for (unsigned long long rm = cm & (cm - 1); rm; rm &= rm - 1) {
       const int jq = __builtin_ctzll(rm);
-      const Key q = key_at(k, jq);
-      if (key_less(q, best)) {
-        best = q;
+      const double qs = mkd(rlu(dlo(k.start), jq), rlu(dhi(k.start), jq));
+      bool less = qs < bs;
+      if (!(qs != bs)) {
+        const int64_t qn = mk64(rlu(lo32(k.nb), jq), rlu(hi32(k.nb), jq));
+        const int64_t bn = mk64(rlu(lo32(k.nb), jb), rlu(hi32(k.nb), jb));
+        less = qn != bn ? qn < bn : rl(k.w, jq) < rl(k.w, jb);
+      }
+      if (less) {
+        bs = qs;
         jb = jq;
       }
     }
+    best.start = bs;
+    best.nb = mk64(rlu(lo32(k.nb), jb), rlu(hi32(k.nb), jb));
+    best.w = rl(k.w, jb);
+    best.comm = mk64(rlu(lo32(k.comm), jb), rlu(hi32(k.comm), jb));
+    if (TR4 && lane == 0 && j == 0) TR(r, 27);
     const int cb = best.w;
     if (j == nf - 1 && nt > 2) {
       // the last frontier decision is made: every touched worker but w and the chosen one
@@ -2707,6 +2762,7 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
     // _add_to_processing (:3199): record, WorkerState.add_to_processing, check_idle_saturated
     o.place(D, x, cb, best.comm, best.start, best.nb, ROUTE_NONROOTISH);
     uint32_t nlc = line_load<LW>(P, cb);
+    if (TR4 && lane == 0 && j == 0) TR(r, 28);
     if (exact) {  // scan mode reads processing_on of this stimulus' earlier placements
       // ... and of t, which left w above: a dependency t shares with x, placed on w, is not
       // needed by t any more (only an exact stimulus, the oldest, scans; the sequencer
@@ -2722,6 +2778,7 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
       const int64_t nb = mk64(rlu(E.z, L2), rlu(E.w, L2));
       dn += needs_inc(D, S, cb, nlc, d, nb, x);
     }
+    if (TR4 && lane == 0 && j == 0) TR(r, 29);
     line_store<LW>(P, cb, nlc);
     const bool isb = lane == jb;
     bool okp = true;
@@ -2730,8 +2787,10 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
       np += 1;
       net += dn;
     }
+    if (TR4 && lane == 0 && j == 0) TR(r, 30);
     if (dn != 0) nbw = isb ? net_bw_of(net, D) : nbw;  // dn is uniform
     if (ballot(!okp)) serr(S, SERR_PREFIX, x);
+    if (TR4 && lane == 0 && j == 0) TR(r, 31);
     if (exact && lane == 0) {  // scan mode reads them for this stimulus' later decisions (the
       D.proc_on[x] = cb;       // sequencer writes them, and the group count, at retirement)
       D.state[x] = S_PROCESSING;
@@ -2776,7 +2835,9 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
     }
     const int qp = S.q_prefix;
     for (int i = 0; i < pops; i++) {
-      const double st = stkj + 0.0 / (double)D.bandwidth;
+      // no transfer: + 0.0 / bandwidth is + 0.0 for the positive bandwidth the engine requires
+      // (the addition stays: it makes -0.0 into +0.0)
+      const double st = stkj + 0.0;
       o.place(D, -1, w, 0, mkd(rlu(dlo(st), jw), rlu(dhi(st), jw)), mk64(rlu(lo32(nbj), jw), rlu(hi32(nbj), jw)),
               ROUTE_ROOTISH_Q);
       bool okq = true;

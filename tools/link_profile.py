@@ -1,6 +1,8 @@
 """Per-link breakdown of the C2 replay's critical chain (GPU, a DGP_TRACE=3 build):
     tools/build_variants.sh trace3 "-DDGP_TRACE=3"
     DGP_LIB=tools/_var/lib_trace3.so python tools/link_profile.py [lo] [n] [c3|c5] [--out file.json]
+A DGP_TRACE=4 build also stamps inside the three largest phases (completion needs, argmin,
+first commit); with -DDGP_SCTA=384 (one executor) the table is the uncontended path's account.
 
 Every traced stimulus records its executor's phases (s_memtime ticks) and which earlier
 stimulus' release made it ready (its completing worker / release holders free: `pred` 0)
@@ -74,15 +76,24 @@ print(f"  wait in place: mean {waited.mean():.0f}, p50 {np.percentile(waited, 50
 rc = T[:, 2] - T[:, 1]
 ok = (T[:, 1] > 0) & (T[:, 2] > 0)
 res["ready_to_claim"] = pct(rc[ok])
-SUB = [(14, 24, "place stores"), (24, 25, "line_load cb"), (25, 26, "needs_inc"), (26, 27, "line_store+dict_add"),
-       (27, 28, "net_bw + ballot"), (28, 29, "occ_dict_r"), (29, 15, "rec stores")]
-sel = (L[:, 24] > 0) & (L[:, 29] > 0) & (nf > 0)
-if sel.any():
-    print("  first commit, split:")
-for a, b, nm in (SUB if sel.any() else ()):  # (only the commit-split probe build records these)
-    d = L[sel, b] - L[sel, a]
-    res["phases"]["commit:" + nm] = pct(d)
-    print(f"    {nm:22s} mean {d.mean():8.0f} p50 {np.percentile(d, 50):8.0f}")
+# (only a DGP_TRACE=4 build records these: stamps inside the three largest phases)
+SUB = [("state -> completion needs", False, [(9, 24, "needs_dec_all"), (24, 25, "needs_reset + line_store w"),
+                                             (25, 26, "dict_add w"), (26, 10, "net_bw_of")]),
+       ("keys -> argmin", True, [(13, 27, "key_at loop"), (27, 14, "early release")]),
+       ("argmin -> first commit", True, [(14, 28, "o.place + line_load cb"), (28, 29, "needs_inc_all"),
+                                         (29, 30, "line_store + dict_add"), (30, 31, "net_bw_of + ballot"),
+                                         (31, 15, "occ_dict_r + o.rec")])]
+for title, front, parts in SUB:
+    sel = (L[:, 24] > 0) & (L[:, 26] > 0)
+    if front:
+        sel = sel & (nf > 0) & (L[:, 27] > 0) & (L[:, 31] > 0)
+    if not sel.any():
+        continue
+    print(f"  {title}, split:")
+    for a, b, nm in parts:
+        d = L[sel, b] - L[sel, a]
+        res["phases"][f"{title}: {nm}"] = pct(d)
+        print(f"    {nm:28s} mean {d.mean():8.0f} p50 {np.percentile(d, 50):8.0f} p90 {np.percentile(d, 90):8.0f}")
 print(f"  ready -> claimed: mean {rc[ok].mean():.0f} p50 {np.percentile(rc[ok], 50):.0f}")
 
 # ---- the critical chain, backwards
