@@ -14,6 +14,13 @@ namespace msg {
 
 __device__ __forceinline__ bool multi_row(const Dev& D, int d) { return (D.evf & EVF_MULTI) && (D.tdyn[d] & TD_MULTI); }
 
+// TaskState.nbytes of a dependency as _task_to_msg sends it: the size its task-finished
+// reported, -1 when it reported none. cur_nbytes is get_nbytes() of a result in memory
+// (default_data_size for an unknown size), so it only says whether d is in memory.
+__device__ __forceinline__ int64_t sent_nbytes(const Dev& D, int d) {
+  return D.cur_nbytes[d] >= 0 ? D.res_nbytes[d] : -1;
+}
+
 __device__ __forceinline__ int who_has_count(const Dev& D, int d) {
   if (multi_row(D, d)) {
     int n = 0;
@@ -56,7 +63,7 @@ __global__ void __launch_bounds__(256) k_msg_fill(const Dev* __restrict__ Dp, lo
   for (int64_t k = D.dep_ptr[t]; k < D.dep_ptr[t + 1]; k++, pos++) {
     const int d = D.dep_idx[k];
     dep_task[pos] = d;
-    dep_nbytes[pos] = D.cur_nbytes[d];
+    dep_nbytes[pos] = sent_nbytes(D, d);
     int n = 0;
     if (multi_row(D, d)) {
       for (int b = 0; b < D.WB; b++) {

@@ -1027,7 +1027,7 @@ __device__ __attribute__((noinline)) bool publish_messages(const Dev& D, svc::Mb
       for (int64_t q = a; q < b; q++, e++) {
         const int d = D.dep_idx[q];
         dtask[e] = d;
-        dnb[e] = D.cur_nbytes[d];
+        dnb[e] = msg::sent_nbytes(D, d);
         hptr[e] = (int32_t)h;
         if (msg::multi_row(D, d)) {
           for (int w8 = 0; w8 < D.WB; w8++)

@@ -17,7 +17,8 @@ field                  dtype       meaning (reference attribute it mirrors)
 ``group_id``           i32         ``TaskState.group`` (``key_split_group``, :1835)
 ``wanted``             u8          ``bool(TaskState.who_wants)`` (client futures)
 ``rootish_override``   i8          ``TaskState._rootish`` (-1 = None, :2940)
-``nbytes``             i64         ``nbytes`` the worker reports on completion
+``nbytes``             i64         ``nbytes`` the worker reports on completion (-1:
+                                   none, ``get_nbytes`` gives ``DEFAULT_DATA_SIZE``)
 ``start/stop``         f64         the task's ``startstops`` compute interval
 ``nthreads``           i32[W]      ``WorkerState.nthreads`` of the simulated workers
 ``prefix_names``       list[str]   TaskPrefix names (index = prefix id)
@@ -218,6 +219,40 @@ def restrict(g: dict, frac: float, *, seed: int = 0, max_valid: int = 8, empty_f
     return g
 
 
+WIDE_SUM_BOUND = 2 ** 53
+
+
+def widen(g: dict, seed: int, *, median: float = 2.0 ** 33, sigma: float = 2.0, unknown_frac: float = 0.1,
+          epoch: float = 1.7e9, known=()) -> dict:
+    """The values of a live cluster on the graph ``g`` (a copy; the structure stays): the
+    fixtures' ``int(lognormal(10, 2))`` outputs and compute intervals from 0.0 keep the high
+    word of every byte count zero and every timestamp small.
+
+    * ``nbytes`` = ``int(lognormal(ln median, sigma))``: with the defaults single values lie on
+      both sides of 2^31 and of 2^32, and a worker's sum passes 2^36 within a few results;
+    * a fraction ``unknown_frac`` of them is -1: the worker reported no size (``nbytes=None``),
+      so ``TaskState.get_nbytes`` (scheduler.py:1478) gives ``DEFAULT_DATA_SIZE``. The tasks
+      in ``known`` keep a size (a shuffle's barrier);
+    * ``start`` is a Unix timestamp, ``epoch`` + U(0, 1000) s, and ``stop`` = start + the
+      graph's own duration: ``stop - start`` is then taken from large doubles.
+
+    The non-negative sizes sum to less than 2^53 (ValueError otherwise): every sum of sizes
+    the reference forms is then exact in a double, and Python's ``int / int`` equals the
+    ``double / double`` of the oracle and the kernels."""
+    rng = np.random.default_rng(seed)
+    n = g["n_tasks"]
+    nb = rng.lognormal(np.log(median), sigma, n).astype(np.int64)
+    unknown = rng.random(n) < unknown_frac
+    unknown[np.asarray(known, np.int64)] = False
+    nb[unknown] = -1
+    if sum(int(x) for x in nb[nb >= 0]) >= WIDE_SUM_BOUND:
+        raise ValueError("widen: the known sizes sum to 2^53 or more")
+    start = epoch + rng.uniform(0.0, 1000.0, n)
+    g = dict(g)
+    g.update(name=g["name"] + "_wide", nbytes=nb, start=start, stop=start + (g["stop"] - g["start"]))
+    return g
+
+
 def star(n_leaves: int, n_workers: int) -> dict:
     """One root and ``n_leaves`` non-rootish leaves that depend on it: the root's completion
     places every leaf on the root's worker (its only candidate, scheduler.py:8550-8593),
@@ -415,7 +450,7 @@ def check_graph(g: dict) -> None:
 
 def steal_problem(n_workers: int, n_tasks: int, *, nthreads: int = 2, hot_frac: float = 0.1, seed: int = 1,
                   n_prefixes: int = 8, zipf_a: float = 1.5, replicas: int = 1, occ_quantum: float = 0.0,
-                  restrict: float = 0.0) -> dict:
+                  restrict: float = 0.0, bandwidth: int = 100_000_000) -> dict:
     """A WorkStealing.balance() input in the shape of BASELINE.json's C4:
     D = T/4 memory-resident dependencies (``int(lognormal(16, 3))`` bytes) on uniform
     workers; T processing tasks with 1-2 of them (5 % dependency-free -> level 0) in
@@ -427,10 +462,10 @@ def steal_problem(n_workers: int, n_tasks: int, *, nthreads: int = 2, hot_frac: 
 
     ``replicas`` > 1 gives every dependency 1..replicas distinct holders (who_has as
     holder_ptr / holder_idx); ``occ_quantum`` > 0 rounds occupancies to that grid, so many
-    thieves tie on stack time."""
+    thieves tie on stack time; ``bandwidth`` is the scheduler's (the reference's default)."""
     rng = np.random.default_rng(seed)
     W, T = int(n_workers), int(n_tasks)
-    bw = 100_000_000
+    bw = int(bandwidth)
     D = max(T // 4, 1)
     hot = rng.choice(W, size=max(int(round(W * hot_frac)), 1), replace=False)
     holder = rng.integers(0, W, D).astype(np.int32)

@@ -26,6 +26,11 @@ SURVEY.md §0): ``worker_objective`` gets the worker index appended as a last ke
 and ``idle_task_count`` / ``saturated`` iterate in ascending worker index. No
 reference arithmetic is changed.
 
+A fixture may carry its own config (``fixtures()``: a third tuple entry overriding
+``DEFAULT_CONFIG``; the ``wide_*`` family, ``WIDE_CONFIG``): ``reference_config`` sets it where
+a deployment would, and a negative graph ``nbytes`` is reported as ``nbytes=None``. Each
+fixture's ``meta`` records its config and the command that made it.
+
 Recorded per placement (at ``_add_to_processing`` :3199, before it mutates):
 task, worker, ``comm_bytes`` (the ``worker_objective`` sum, :3136-3138), the
 objective's ``start_time`` (:3140-3141), ``ws.nbytes`` and the route taken
@@ -161,6 +166,9 @@ def build_state(g, cfg, addr_of=None):
     s.idle_task_count = IdxSet()
     s.saturated = IdxSet()
     assert s.bandwidth == cfg["bandwidth"]
+    # a fixture's own values (reference_config) have reached the reference
+    assert s.UNKNOWN_TASK_DURATION == cfg.get("unknown_duration", 0.5)
+    assert distributed.scheduler.DEFAULT_DATA_SIZE == cfg.get("default_data_size", 1024)
     for i in range(W):
         addr = addr_of(i)
         widx[addr] = i
@@ -264,7 +272,7 @@ def replay(g, cfg):
             i = tidx[t]
             sid = f"task-finished-{i}"
             r, cm, wm = s._transition(
-                t, "memory", sid, worker=ts.processing_on.address, nbytes=int(g["nbytes"][i]),
+                t, "memory", sid, worker=ts.processing_on.address, nbytes=report_nbytes(g["nbytes"][i]),
                 type=None, typename="int",
                 startstops=[{"action": "compute", "start": float(g["start"][i]), "stop": float(g["stop"][i])}])
             n0 = len(rec["task"])
@@ -279,16 +287,52 @@ def replay(g, cfg):
 
 
 
-def config_dict(saturation):
-    return {
-        "bandwidth": int(dask.config.get("distributed.scheduler.bandwidth")),
-        "default_data_size": 1024,
-        "unknown_duration": 0.5,
-        "saturation": saturation,
-    }
+def report_nbytes(x):
+    """The ``nbytes`` of a task-finished report: a negative graph value is a result whose size
+    the worker did not report, ``nbytes=None`` (``_transition`` then leaves ``ts.nbytes`` at
+    -1, scheduler.py:2427-2428; ``set_nbytes(-1)`` would subtract from ``ws.nbytes``)."""
+    return int(x) if x >= 0 else None
 
 
-def save(name, g, cfg, rec, rounds, nplaced, states, secs):
+DEFAULT_CONFIG = {"bandwidth": 100_000_000, "default_data_size": 1024, "unknown_duration": 0.5}
+# the wide_* / svc*_wide_* fixtures: none of the engine's built-in defaults; a bandwidth that is
+# no power of ten and keeps the transfer terms of multi-GB results near the task durations
+WIDE_CONFIG = {"bandwidth": 12_345_678_901, "default_data_size": 5_000_000_000, "unknown_duration": 0.02}
+
+
+def config_dict(saturation, **overrides):
+    """A fixture's config: the reference's defaults, or the fixture's own values."""
+    cfg = dict(DEFAULT_CONFIG, saturation=saturation)
+    cfg.update(overrides)
+    return cfg
+
+
+class reference_config:
+    """``with reference_config(cfg):`` the reference reads ``cfg`` where a deployment sets it:
+    the bandwidth and the unknown-task duration from dask's config when the state is built
+    (scheduler.py:1712, :1757), the saturation likewise, and ``DEFAULT_DATA_SIZE`` as the
+    module-level value ``TaskState.get_nbytes`` reads at call time (:173, :1478), set for the
+    run and restored after it. No reference arithmetic changes."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+
+    def __enter__(self):
+        c = self.cfg
+        self._dask = dask.config.set({"distributed.scheduler.worker-saturation": c["saturation"],
+                                      "distributed.scheduler.bandwidth": int(c["bandwidth"]),
+                                      "distributed.scheduler.unknown-task-duration": float(c["unknown_duration"])})
+        self._dask.__enter__()
+        self._dds = distributed.scheduler.DEFAULT_DATA_SIZE
+        distributed.scheduler.DEFAULT_DATA_SIZE = int(c["default_data_size"])
+        return c
+
+    def __exit__(self, *exc):
+        distributed.scheduler.DEFAULT_DATA_SIZE = self._dds
+        self._dask.__exit__(*exc)
+
+
+def save(name, g, cfg, rec, rounds, nplaced, states, secs, generator=None):
     R = len(rounds)
     out = {k: g[k] for k in ("dep_ptr", "dep_idx", "prio", "prefix_id", "group_id", "wanted",
                              "rootish_override", "nbytes", "start", "stop", "nthreads",
@@ -311,7 +355,7 @@ def save(name, g, cfg, rec, rounds, nplaced, states, secs):
     meta = dict(name=name, prefix_names=list(g["prefix_names"]), group_names=list(g["group_names"]),
                 config=dict(cfg, saturation=("inf" if math.isinf(sat) else sat)),
                 reference_seconds=secs, n_placements=len(rec["task"]), n_rounds=R,
-                generator="tests/golden/gen_golden.py", python=sys.version.split()[0],
+                generator=generator or "tests/golden/gen_golden.py", python=sys.version.split()[0],
                 dask=dask.__version__)
     out["meta"] = np.array(json.dumps(meta))
     path = os.path.join(HERE, f"{name}.npz")
@@ -407,6 +451,7 @@ def fixtures():
         "restr_noworker_sat1.1": (lambda: graphs.restrict(graphs.random_dag(5000, 64, seed=57), 0.2, seed=58),
                                   1.1),
         **edge_fixtures(),
+        **wide_fixtures(),
     }
 
 
@@ -470,6 +515,39 @@ def edge_fixtures():
     }
 
 
+def wide_fixtures():
+    """The ``wide_*`` family: the values of a live cluster (graphs.widen: results of several
+    GB on both sides of 2^31 and 2^32, sizes the worker did not report, Unix timestamps)
+    under a config that is none of the engine's built-in defaults (WIDE_CONFIG). What each
+    one contains is asserted by tests/test_wide_values.py."""
+    inf = math.inf
+    W = graphs.widen
+
+    def var_dag(n, w, seed, k=3):
+        return graphs.random_dag(n, w, seed=seed, n_inner_prefixes=k, random_durations=True, nthreads="random")
+
+    return {
+        "wide_c2var_sat1.1": (lambda: W(var_dag(2500, 64, 801), 811), 1.1, WIDE_CONFIG),
+        "wide_c2var_satinf": (lambda: W(var_dag(2500, 64, 802), 812), inf, WIDE_CONFIG),
+        "wide_restr_sat1.1": (lambda: W(graphs.restrict(var_dag(2500, 48, 803), 0.25, seed=804, max_valid=12,
+                                                        empty_frac=0.0), 1813),
+                              1.1, WIDE_CONFIG),
+        # more than 32 prefixes: the round-kernel engine. One thread per worker: transfer terms of
+        # seconds gather work on few workers, and no worker may run more than 8 prefixes at
+        # once (the engines' per-worker dict of 8 slots, DESIGN "out of scope"; asserted by
+        # test_wide_values.py)
+        "wide_p40_sat1.1": (lambda: W(graphs.random_dag(2000, 48, seed=835, n_inner_prefixes=39,
+                                                        random_durations=True), 1815), 1.1, WIDE_CONFIG),
+        # the edge_scan_refill shape: needs_what tables in scan mode
+        "wide_scan_refill_sat1.1": (lambda: W(graphs.layered_dag(12, 200, 3, seed=841, fanins=(7, 8), span=2,
+                                                                 n_inner_prefixes=3, random_durations=True,
+                                                                 nthreads="random"), 1816), 1.1, WIDE_CONFIG),
+        # DEFAULT_DATA_SIZE = 0, the least value the ABI takes, with 30 % unknown sizes
+        "wide_dds0_sat1.1": (lambda: W(var_dag(2500, 64, 807), 4817, unknown_frac=0.3), 1.1,
+                             dict(WIDE_CONFIG, default_data_size=0)),
+    }
+
+
 def no_dep_groups(n_workers, n_groups, group_size, n_agg, seed, nthreads=1):
     """The no-dependency fast path of ``decide_worker_non_rootish`` (scheduler.py:2283-2305):
     small groups of dependency-free tasks (``len(tg) <= 2 * total_nthreads``: not root-ish)
@@ -522,13 +600,13 @@ def occupancy_comm_graph():
 def main(names):
     fx = fixtures()
     for name in names or fx:
-        mk, sat = fx[name]
+        mk, sat, *own = fx[name]
         g = mk()
         graphs.check_graph(g)
-        dask.config.set({"distributed.scheduler.worker-saturation": sat})
-        cfg = config_dict(sat)
-        s, rec, rounds, nplaced, states, secs = replay(g, cfg)
-        save(name, g, cfg, rec, rounds, nplaced, states, secs)
+        with reference_config(config_dict(sat, **(own[0] if own else {}))) as cfg:
+            s, rec, rounds, nplaced, states, secs = replay(g, cfg)
+        save(name, g, cfg, rec, rounds, nplaced, states, secs,
+             generator=f"PYTHONHASHSEED=0 python3.9 tests/golden/gen_golden.py {name}")
 
 
 if __name__ == "__main__":

@@ -57,6 +57,23 @@ import numpy as np  # noqa: E402
 ACCEPTED, FREE_KEYS, ADD_KEYS, RELEASE, UNKNOWN_WORKER = 0, 1, 2, 3, 4
 
 
+def own_config(name, sat):
+    """A case's config: the ``*_wide_*`` streams run under G.WIDE_CONFIG, the others under the
+    reference's defaults."""
+    return G.config_dict(sat, **(G.WIDE_CONFIG if "_wide_" in name else {}))
+
+
+def command(family, name):
+    return f"PYTHONHASHSEED=0 python3.9 tests/golden/gen_service.py {family} {name}"
+
+
+def wide_dag(n, w, seed, wseed):
+    """The c2var shape (2 inner prefixes, random durations, 1-4 threads) with graphs.widen's
+    values: results of several GB, a tenth of them of unknown size, Unix timestamps."""
+    return G.graphs.widen(G.graphs.random_dag(n, w, seed=seed, n_inner_prefixes=2, random_durations=True,
+                                              nthreads="random"), wseed)
+
+
 def replay_service(g, cfg, seed, p_inject=0.35, p_steal=0.0):
     from distributed.scheduler import Scheduler
 
@@ -132,7 +149,7 @@ def replay_service(g, cfg, seed, p_inject=0.35, p_steal=0.0):
             sid = f"task-finished-{len(msgs['task'])}"
             k0 = called["add_keys"]
             r, cm, wm = s.stimulus_task_finished(
-                key, addr[w], sid, run_id + run0 if ref_run is None else ref_run, nbytes=nbytes, type=None, typename="int", metadata=None,
+                key, addr[w], sid, run_id + run0 if ref_run is None else ref_run, nbytes=G.report_nbytes(nbytes), type=None, typename="int", metadata=None,
                 startstops=[{"action": "compute", "start": start, "stop": stop}])
             if called["add_keys"] > k0:
                 st = ADD_KEYS
@@ -296,7 +313,7 @@ def replay_add_workers(g, cfg, seed, n_add, max_nthreads=4, interleave=False, n_
             w = widx[ts.processing_on.address]
             sid = f"task-finished-{len(msgs['task'])}"
             r, cm, wm = s.stimulus_task_finished(
-                ts.key, ts.processing_on.address, sid, int(ts.run_id), nbytes=int(g["nbytes"][t]), type=None,
+                ts.key, ts.processing_on.address, sid, int(ts.run_id), nbytes=G.report_nbytes(g["nbytes"][t]), type=None,
                 typename="int", metadata=None,
                 startstops=[{"action": "compute", "start": float(g["start"][t]), "stop": float(g["stop"][t])}])
             assert ts.state != "processing"
@@ -343,17 +360,18 @@ def main_add_workers(only):
                                  dict(interleave=True, n_paused=4)),
         "svcaddw_order_satinf": (lambda: G.graphs.random_dag(3000, 32, seed=28), float("inf"), 12, 16,
                                  dict(interleave=True, n_paused=3)),
+        # a live cluster's values under a config of its own (graphs.widen, G.WIDE_CONFIG)
+        "svcaddw_wide_sat1.1": (lambda: wide_dag(1500, 24, 906, 916), 1.1, 13, 12),
     }
     for name, (mk, sat, seed, n_add, *kw) in cases.items():
         if only and name not in only:
             continue
         g = mk()
         G.graphs.check_graph(g)
-        dask.config.set({"distributed.scheduler.worker-saturation": sat})
-        cfg = G.config_dict(sat)
-        rec, rounds, nplaced, states, msgs, round_ptr, added = replay_add_workers(g, cfg, seed, n_add,
-                                                                                 **(kw[0] if kw else {}))
-        G.save(name, g, cfg, rec, rounds, nplaced, states, 0.0)
+        with G.reference_config(own_config(name, sat)) as cfg:
+            rec, rounds, nplaced, states, msgs, round_ptr, added = replay_add_workers(g, cfg, seed, n_add,
+                                                                                     **(kw[0] if kw else {}))
+        G.save(name, g, cfg, rec, rounds, nplaced, states, 0.0, generator=command("add-workers", name))
         path = os.path.join(HERE, f"{name}.npz")
         z = dict(np.load(path, allow_pickle=False))
         z.update(msg_task=np.array(msgs["task"], np.int32), msg_worker=np.array(msgs["worker"], np.int32),
@@ -524,7 +542,7 @@ def replay_second_graph(g, g2, cfg, seed, at_frac, n_add=0, dep_frac=0.0, restr=
             w = widx[ts.processing_on.address]
             sid = f"task-finished-{len(msgs['task'])}"
             r, cm, wm = s.stimulus_task_finished(
-                ts.key, ts.processing_on.address, sid, int(ts.run_id), nbytes=int(nb[t]), type=None,
+                ts.key, ts.processing_on.address, sid, int(ts.run_id), nbytes=G.report_nbytes(nb[t]), type=None,
                 typename="int", metadata=None,
                 startstops=[{"action": "compute", "start": float(a0[t]), "stop": float(b0[t])}])
             assert ts.state != "processing"
@@ -772,7 +790,7 @@ def replay_later_graphs(g, later, cfg, at_fracs):
             w = widx[ts.processing_on.address]
             sid = f"task-finished-{len(msgs['task'])}"
             r, cm, wm = s.stimulus_task_finished(
-                ts.key, ts.processing_on.address, sid, int(ts.run_id), nbytes=int(nb[t]), type=None,
+                ts.key, ts.processing_on.address, sid, int(ts.run_id), nbytes=G.report_nbytes(nb[t]), type=None,
                 typename="int", metadata=None,
                 startstops=[{"action": "compute", "start": float(a0[t]), "stop": float(b0[t])}])
             n0 = len(rec["task"])
@@ -1112,7 +1130,7 @@ def replay_events(g, cfg, seed, p_event=0.08, kinds=(1, 2, 3, 4, 5, 6, 7), bw_sc
             if w in removed:
                 return
             ws = s.workers[addr[w]]
-            total = float(rng.uniform(1 - bw_scale, 1 + bw_scale) * 1e8)
+            total = float(rng.uniform(1 - bw_scale, 1 + bw_scale) * cfg["bandwidth"])
             # Scheduler.heartbeat_worker :4223-4226 (bandwidth EWMA)
             frac = 1 / len(s.workers)
             s.bandwidth = s.bandwidth * (1 - frac) + total * frac
@@ -1337,7 +1355,7 @@ def replay_events(g, cfg, seed, p_event=0.08, kinds=(1, 2, 3, 4, 5, 6, 7), bw_sc
             w = widx[ts.processing_on.address]
             sid = f"task-finished-{len(ev['kind'])}"
             r, cm, wm = s.stimulus_task_finished(
-                ts.key, ts.processing_on.address, sid, int(ts.run_id), nbytes=int(g["nbytes"][t]), type=None,
+                ts.key, ts.processing_on.address, sid, int(ts.run_id), nbytes=G.report_nbytes(g["nbytes"][t]), type=None,
                 typename="int", metadata=None,
                 startstops=[{"action": "compute", "start": float(g["start"][t]), "stop": float(g["stop"][t])}])
             assert ts.state != "processing"
@@ -1479,7 +1497,7 @@ def replay_p2p(g, cfg, dumps):
                 continue
             sid_ = f"task-finished-{len(ev['kind'])}"
             r, cm, wm = s.stimulus_task_finished(
-                ts.key, ts.processing_on.address, sid_, int(ts.run_id), nbytes=int(g["nbytes"][t]), type=None,
+                ts.key, ts.processing_on.address, sid_, int(ts.run_id), nbytes=G.report_nbytes(g["nbytes"][t]), type=None,
                 typename="int", metadata=None,
                 startstops=[{"action": "compute", "start": float(g["start"][t]), "stop": float(g["stop"][t])}])
             n0 = len(rec["task"])
@@ -1535,16 +1553,18 @@ def main_events(only):
         # a denser event mix on a smaller graph
         "svcev_dense_sat1.0": (lambda: G.graphs.random_dag(1500, 24, seed=43, n_inner_prefixes=2,
                                                             random_durations=True), 1.0, 43, 0.3),
+        # replicas, long-running tasks and heartbeats that move the bandwidth, at a live
+        # cluster's values under a config of its own (graphs.widen, G.WIDE_CONFIG)
+        "svcev_wide_sat1.1": (lambda: wide_dag(1500, 24, 901, 911), 1.1, 44, 0.3),
     }
     for name, (mk, sat, seed, p_event) in cases.items():
         if only and name not in only:
             continue
         g = mk()
         G.graphs.check_graph(g)
-        dask.config.set({"distributed.scheduler.worker-saturation": sat})
-        cfg = G.config_dict(sat)
-        rec, rounds, nplaced, states, ev, hb, round_ptr = replay_events(g, cfg, seed, p_event)
-        G.save(name, g, cfg, rec, rounds, nplaced, states, 0.0)
+        with G.reference_config(own_config(name, sat)) as cfg:
+            rec, rounds, nplaced, states, ev, hb, round_ptr = replay_events(g, cfg, seed, p_event)
+        G.save(name, g, cfg, rec, rounds, nplaced, states, 0.0, generator=command("events", name))
         path = os.path.join(HERE, f"{name}.npz")
         z = dict(np.load(path, allow_pickle=False))
         z.update(ev_kind=np.array(ev["kind"], np.int8), ev_task=np.array(ev["task"], np.int32),
@@ -1604,25 +1624,32 @@ def main_resync(only):
         # allowed_failures 0: every processing task of a lost worker errs
         "svcwl_killed0_c2var_sat1.1": (lambda: G.graphs.random_dag(3000, 48, seed=61, n_inner_prefixes=3,
                                                                     random_durations=True, nthreads="random"), 1.1, 61, 0.12),
+        # a live cluster's values under a config of its own (graphs.widen, G.WIDE_CONFIG): the
+        # resync rows, a lost worker's bytes and sole replicas, releases subtracting results of
+        # several GB
+        "svcrs_wide_sat1.1": (lambda: wide_dag(1500, 24, 902, 912), 1.1, 71, 0.1),
+        "svcwl_chain_wide_sat1.1": (lambda: wide_dag(1500, 24, 903, 913), 1.1, 72, 0.12),
+        "svcrel_wide_sat1.1": (lambda: wide_dag(1500, 24, 904, 914), 1.1, 73, 0.15),
+        "svccan_wide_sat1.1": (lambda: wide_dag(1500, 24, 905, 915), 1.1, 74, 0.15),
     }
     for name, (mk, sat, seed, p_event) in cases.items():
         if only and name not in only:
             continue
         g = mk()
         G.graphs.check_graph(g)
-        dask.config.set({"distributed.scheduler.worker-saturation": sat})
-        cfg = G.config_dict(sat)
+        cfg = own_config(name, sat)
         dumps = []
         kinds_ = ((1, 2, 3, 4, 5, 6, 7, EV_RETIRE, EV_RETIRE, EV_PAUSE) if name.startswith("svcrt_") else
                   (1, 2, 3, 4, 5, 6, 7, EV_LOSE_WORKER, EV_LOSE_WORKER, EV_RESUME) if name.startswith("svcwl_") else
                   (1, 2, 3, 4, 5, 6, 7, EV_RELEASE_KEYS, EV_RELEASE_KEYS) if name.startswith(("svcrel_", "svccan_"))
                   else (1, 2, 3, 4, 5, 6, 7, EV_ERRED_RETRY, EV_ERRED_RETRY) if name.startswith("svcretry_")
                   else kinds)
-        rec, rounds, nplaced, states, ev, hb, round_ptr = replay_events(
-            g, cfg, seed, p_event, kinds_, dumps=dumps, chains=name.startswith(("svcwl_chain_", "svcwl_killed")),
-            allowed_failures=loss_allowed_failures(name), release_memory=name.startswith("svcrel_"),
-            release_cancel=name.startswith("svccan_"))
-        G.save(name, g, cfg, rec, rounds, nplaced, states, 0.0)
+        with G.reference_config(cfg):
+            rec, rounds, nplaced, states, ev, hb, round_ptr = replay_events(
+                g, cfg, seed, p_event, kinds_, dumps=dumps, chains=name.startswith(("svcwl_chain_", "svcwl_killed")),
+                allowed_failures=loss_allowed_failures(name), release_memory=name.startswith("svcrel_"),
+                release_cancel=name.startswith("svccan_"))
+        G.save(name, g, cfg, rec, rounds, nplaced, states, 0.0, generator=command("resync", name))
         path = os.path.join(HERE, f"{name}.npz")
         z = dict(np.load(path, allow_pickle=False))
         z.update(ev_kind=np.array(ev["kind"], np.int8), ev_task=np.array(ev["task"], np.int32),

@@ -22,8 +22,8 @@ BW = 100_000_000
 LATENCY = 0.1  # distributed/stealing.py:25
 
 
-def sweep_problem(nb=1000, span=6):
-    transfer = nb / BW + LATENCY
+def sweep_problem(nb=1000, span=6, bw=BW):
+    transfer = nb / bw + LATENCY
     durs = []
     for k in range(-1, 17):
         target = 2.0 ** (k - 5.5)
@@ -39,7 +39,7 @@ def sweep_problem(nb=1000, span=6):
     W = 4
     p = dict(nthreads=np.full(W, 2, np.int32), occ=np.array([50.0, 0.0, 1.0, 2.0]), nproc=np.array([T, 0, 1, 1], np.int32),
              wnbytes=np.zeros(W, np.int64), idle=np.array([0, 1, 0, 0], np.uint8), sat=np.array([1, 0, 0, 0], np.uint8),
-             total_occ=53.0, total_nthreads=2 * W, bandwidth=BW, victim=np.zeros(T, np.int32), duration=durs,
+             total_occ=53.0, total_nthreads=2 * W, bandwidth=bw, victim=np.zeros(T, np.int32), duration=durs,
              fast=np.zeros(T, np.uint8), dep_ptr=np.arange(T + 1, dtype=np.int64), dep_idx=np.zeros(T, np.int32),
              data_nbytes=np.array([nb], np.int64), data_get_nbytes=np.array([nb], np.int64),
              data_holder=np.array([0], np.int32))
@@ -72,6 +72,35 @@ def test_sweep_hits_half_integers():
 def test_oracle_levels_at_boundaries():
     p = sweep_problem()
     assert np.array_equal(oracle.steal_balance(p)["level"], reference_levels(p))
+
+
+# other bandwidths than the reference's default (a deployment's distributed.scheduler.bandwidth;
+# the extension passes the live scheduler's), with a dependency whose transfer is not latency
+# alone: 5 GB (past 2^32 bytes) at 12.5 GB/s, 1 kB and 3 GB at 1 MB/s
+OTHER_BW = [(12_500_000_000, 5_000_000_000), (12_500_000_000, 1000), (1_000_000, 1000), (1_000_000, 3_000_000_000)]
+
+
+@pytest.mark.parametrize("bw,nb", OTHER_BW)
+def test_oracle_levels_at_boundaries_other_bandwidths(bw, nb):
+    p = sweep_problem(nb=nb, bw=bw)
+    want = reference_levels(p)
+    assert len(set(want.tolist())) >= 10  # the sweep still crosses the levels
+    assert np.array_equal(oracle.steal_balance(p)["level"], want)
+    if nb > 1000:  # the default bandwidth would give other levels
+        assert not np.array_equal(reference_levels(dict(p, bandwidth=BW)), want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bw,nb", OTHER_BW)
+def test_device_levels_at_boundaries_other_bandwidths(bw, nb):
+    from distributed_amd.engine import PlacementEngine
+
+    p = sweep_problem(nb=nb, bw=bw)
+    with PlacementEngine(0) as eng:
+        got = eng.steal_balance(p)["level"]
+    want = reference_levels(p)
+    bad = np.nonzero(got != want)[0]
+    assert len(bad) == 0, [(float(p["duration"][i]), int(got[i]), int(want[i])) for i in bad[:5]]
 
 
 @pytest.mark.gpu
