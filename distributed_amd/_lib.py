@@ -21,6 +21,8 @@ _i32p = C.POINTER(C.c_int32)
 # name -> (restype, argtypes); the list is also what tests check the library exports
 SIGNATURES = {
     "dgp_abi_version": (C.c_int, []),
+    "dgp_abi_revision": (C.c_int, []),
+    "dgp_num_unrunnable": (C.c_int64, [_P]),
     "dgp_create": (_P, [C.c_int]),
     "dgp_destroy": (None, [_P]),
     "dgp_last_error": (C.c_char_p, [_P]),
@@ -101,6 +103,7 @@ SIGNATURES = {
 }
 
 ABI_VERSION = 22
+ABI_REVISION = 1  # entry points added to ABI 22 (include/dgplace.h DGP_ABI_REVISION)
 _libs: dict = {}
 
 
@@ -132,5 +135,7 @@ def load() -> C.CDLL:
         fn.argtypes = args
     if lib.dgp_abi_version() != ABI_VERSION:
         raise DgpError(f"{os.path.basename(path)} ABI {lib.dgp_abi_version()} != {ABI_VERSION}")
+    if lib.dgp_abi_revision() != ABI_REVISION:
+        raise DgpError(f"{os.path.basename(path)} ABI revision {lib.dgp_abi_revision()} != {ABI_REVISION}")
     _libs[path] = lib
     return lib

@@ -608,6 +608,7 @@ int run_service_stimuli(dgp_engine* e) {
 extern "C" {
 
 int dgp_abi_version(void) { return DGP_ABI_VERSION; }
+int dgp_abi_revision(void) { return DGP_ABI_REVISION; }
 
 dgp_engine* dgp_create(int device) {
   int n = 0;
@@ -2421,6 +2422,13 @@ int dgp_set_worker_status(dgp_engine* e, int32_t worker, int32_t running, int64_
   }, n_new_placements);
 }
 
+int64_t dgp_num_unrunnable(dgp_engine* e) {
+  if (!e || resident_stop(e)) return -1;
+  dgp::Ctl c;
+  if (read_ctl(e, &c)) return -1;
+  return (int64_t)c.n_unrunnable;
+}
+
 int dgp_long_running(dgp_engine* e, int32_t task, double compute_duration, int64_t* n_new_placements) {
   if (int rc_ = resident_stop(e)) return rc_;
   if (n_new_placements) *n_new_placements = 0;
@@ -2963,6 +2971,12 @@ int dgp_sync_globals(dgp_engine* e, int64_t n_tasks_counter, double network_occ_
   }
   c.qhead = 0;
   c.qlen = n_queued;
+  {  // |unrunnable| from the task rows handed over (dgp_sync_tasks came first): the scheduler may
+     // have moved tasks into or out of no-worker meanwhile
+    std::vector<uint8_t> st((size_t)D.N);
+    HIPCHK(e, hipMemcpy(st.data(), D.state, (size_t)D.N, hipMemcpyDeviceToHost));
+    c.n_unrunnable = (long long)std::count(st.begin(), st.end(), (uint8_t)dgp::S_NO_WORKER);
+  }
   HIPCHK(e, hipMemcpy(e->ctl, &c, sizeof c, hipMemcpyHostToDevice));
   if (n_queued) HIPCHK(e, hipMemcpy(D.qarr, queued, n_queued * 4, hipMemcpyHostToDevice));
   for (double* p : {D.pdur_cur, D.pdur_walk, D.pdur_pre})

@@ -114,7 +114,9 @@ class PlacementEngine:
     def _check(self, rc: int, what: str):
         if rc != 0:
             msg = self.lib.dgp_last_error(self.h)
-            raise _lib.DgpError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            err = _lib.DgpError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            err.code = rc  # include/dgplace.h DGP_E_*
+            raise err
 
     def close(self):
         if getattr(self, "h", None):
@@ -461,6 +463,13 @@ class PlacementEngine:
         self._check(self.lib.dgp_set_worker_status(self.h, int(worker), int(running), C.byref(n)),
                     "dgp_set_worker_status")
         return int(n.value)
+
+    def num_unrunnable(self) -> int:
+        """|SchedulerState.unrunnable| as the engine holds it (Ctl.n_unrunnable)."""
+        n = int(self.lib.dgp_num_unrunnable(self.h))
+        if n < 0:
+            raise _lib.DgpError("dgp_num_unrunnable failed")
+        return n
 
     def long_running(self, task: int, compute_duration: float = math.nan) -> int:
         """handle_long_running (:5817-5848); NaN = compute_duration None."""

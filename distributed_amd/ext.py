@@ -402,6 +402,9 @@ class GPUPlacementExtension(SchedulerPlugin):
         # partial is one Python frame less per decision than a closure
         table[("waiting", "processing")] = functools.partial(self._transition_waiting_processing, ref=ref_wp)
         table[("queued", "processing")] = functools.partial(self._transition_queued_processing, ref=ref_qp)
+        ref_np = table.get(("no-worker", "processing"))
+        if ref_np is not None:
+            table[("no-worker", "processing")] = functools.partial(self._transition_no_worker_processing, ref=ref_np)
         s._TRANSITIONS_TABLE = table  # per instance: the class table stays untouched
         if not getattr(s, "_gpu_placement_add", False):
             ref_add = s._add_to_processing
@@ -1191,12 +1194,14 @@ class GPUPlacementExtension(SchedulerPlugin):
         return _REF
 
     @staticmethod
-    def _route_of(sched, ts, queued: bool) -> int:
+    def _route_of(sched, ts, queued: bool, non_rootish: bool = False) -> int:
         """The decide_worker route the scheduler's own decision takes (include/dgplace.h
-        DGP_ROUTE_*; the routes of tests/golden/gen_golden.py)."""
+        DGP_ROUTE_*; the routes of tests/golden/gen_golden.py). ``non_rootish``: the
+        transition decides with decide_worker_non_rootish whatever the task (no-worker ->
+        processing, :2128)."""
         if queued:
             return 1
-        if sched.is_rootish(ts):
+        if not non_rootish and sched.is_rootish(ts):
             return 2 if math.isinf(sched.WORKER_SATURATION) else 1
         if ts.dependencies or sched.valid_workers(ts) is not None or len(sched.running) < len(sched.workers):
             return 0
@@ -1244,6 +1249,15 @@ class GPUPlacementExtension(SchedulerPlugin):
             return {}, {}, {}
         sched.queued.discard(ts)
         return sched._add_to_processing(ts, ws, stimulus_id=stimulus_id)
+
+    def _transition_no_worker_processing(self, sched, key, stimulus_id, ref=None, **kwargs):
+        """_transition_no_worker_processing (scheduler.py:2121-2133) is always the scheduler's
+        own (the engine does not schedule no-worker tasks): under a suspension the placement
+        it makes is recorded with decide_worker_non_rootish's route, which the reference
+        takes here whatever the task (:2128)."""
+        if self.active and self.suspended:
+            self._route = self._route_of(sched, sched.tasks[key], False, non_rootish=True)
+        return ref(sched, key, stimulus_id)
 
     # ----------------------------------------------------------- plugin hooks
     def transition(self, key, start, finish, *args, stimulus_id=None, **kwargs):
@@ -1631,9 +1645,38 @@ class GPUPlacementExtension(SchedulerPlugin):
         if wi is None:
             self.fallback(f"worker-status-change of {ws.address}: not in the engine's table")
             return
+        if name == "running" and getattr(s, "unrunnable", None) and self._resume_schedules(ws):
+            # the handler is about to recommend no-worker tasks to processing
+            # (bulk_schedule_unrunnable_after_adding_worker :5872-5878), which the engine does not
+            # model: the scheduler decides this stimulus, the resync brings the worker's status
+            # and the tasks' states. (Unnoticed, the engine would leave them no-worker and the
+            # first decision the scheduler asked for would end GPU placement for the session.)
+            self.stats["resume_unrunnable"] += 1
+            self._suspend(f"worker-status-change of {ws.address}: no-worker tasks are scheduled on it")
+            return
         self._engine_op("set_worker_status", wi, 1 if name == "running" else 0)
         if self.active and name == "running":
             self._window = (_ADD_WORKER_TRANSITIONS, None)
+
+    def _resume_schedules(self, ws) -> bool:
+        """bulk_schedule_unrunnable_after_adding_worker(ws) (scheduler.py:3173-3186) would
+        recommend a task, as the handler is about to evaluate it: an unrunnable task whose
+        valid_workers is None or holds ``ws``, with ``ws`` in ``running`` as it is by then
+        (:5873; valid_workers intersects with it, :3105-3106)."""
+        s = self.scheduler
+        running = getattr(s, "running", None)
+        added = running is not None and ws not in running
+        if added:
+            running.add(ws)
+        try:
+            for ts in s.unrunnable:
+                valid = s.valid_workers(ts)
+                if valid is None or ws in valid:
+                    return True
+            return False
+        finally:
+            if added:
+                running.discard(ws)
 
     def _on_reschedule(self, kw):
         """reschedule (Scheduler._reschedule :7900-7924, the worker's Reschedule): a processing

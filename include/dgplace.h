@@ -71,6 +71,9 @@ extern "C" {
 #endif
 
 #define DGP_ABI_VERSION 22
+/* Entry points added since, every ABI 22 signature unchanged (a caller built against ABI 22
+ * runs as before): 1 = dgp_num_unrunnable. */
+#define DGP_ABI_REVISION 1
 
 #define DGP_OK 0
 #define DGP_E_ARG -1     /* invalid argument / shape */
@@ -97,6 +100,7 @@ extern "C" {
 typedef struct dgp_engine dgp_engine;
 
 int dgp_abi_version(void);
+int dgp_abi_revision(void);
 
 /* Create an engine on HIP device `device`. Returns NULL on failure (no device). */
 dgp_engine* dgp_create(int device);
@@ -373,6 +377,13 @@ int dgp_remove_replicas(dgp_engine* e, int64_t n, const int32_t* task, const int
  * idle, idle_task_count and saturated: never a decide_worker candidate, its completions are
  * still accepted); running = 1 runs it again (check_idle_saturated, then the queue refill). */
 int dgp_set_worker_status(dgp_engine* e, int32_t worker, int32_t running, int64_t* n_new_placements);
+/* |SchedulerState.unrunnable| as the engine holds it (read-only; -1 on error). A worker that
+ * runs again does not schedule no-worker tasks on the device
+ * (bulk_schedule_unrunnable_after_adding_worker :3173-3186, :5872-5878 is not modelled): while
+ * the scheduler has any, the caller lets it decide a resume and hands its state over
+ * (dgp_sync_*); dgp_add_worker(_at) refuses a join while this is not 0. dgp_sync_globals
+ * recounts it from the task rows. */
+int64_t dgp_num_unrunnable(dgp_engine* e);
 
 /* Scheduler.handle_long_running(task, compute_duration): the task's prefix duration average
  * takes compute_duration (NaN: None), WorkerState.add_to_long_running (:747-757: the prefix
