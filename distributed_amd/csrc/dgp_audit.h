@@ -44,7 +44,7 @@ struct Scratch {
   uint8_t* scan;       // [W] the worker's needs_what is in scan mode
   // inputs from the host
   const uint8_t* status;    // [W] 0 running, 1 paused, 2 removed (the engine's host copy)
-  const int32_t* base_cap;  // [W] max(ceil(saturation * max(nthreads, 1)), 1), 0 under inf
+  const int32_t* base_cap;  // [W] max(ceil(saturation * nthreads), 1), 0 under inf (rows::base_cap)
   // output
   unsigned long long* n_viol;
   dgp_violation* out;
@@ -498,6 +498,43 @@ __global__ void __launch_bounds__(256) k_au_row_needs(const Dev* __restrict__ Dp
       report(A, ln == 0 && d != x, DGP_AR_ROW_WORKERS, DGP_AF_NEEDS_COUNT, w, x >> 8, d & 0xffu, x & 0xffu);
     }
     report(A, e != 0 && !matched, DGP_AR_ROW_WORKERS, DGP_AF_NEEDS_COUNT, w, e >> 8, e & 0xffu, 0);
+  }
+}
+
+// The task rows of dgp_audit_tasks (normalised and range-checked by the host, dgp_rows.h), one
+// thread per row: every field k_sync_tasks would write against what the engine holds. What
+// follows from a row comes from the function k_sync_tasks itself calls (rows::derive_task; its
+// who_has words go to who[i * WB ..], scratch). The columns a kernel reads only in some states
+// are compared for the rows in those states (include/dgplace.h).
+__global__ void __launch_bounds__(256) k_au_row_tasks(const Dev* __restrict__ Dp, const rows::TaskRow* __restrict__ row,
+                                                      long long n, const int32_t* __restrict__ holders,
+                                                      unsigned long long* __restrict__ who, Scratch A) {
+  const Dev& D = *Dp;
+  const long long step = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+    const rows::TaskRow r = row[i];
+    const int t = r.t;
+    const uint8_t s = r.state;
+    unsigned long long* x = who + (size_t)i * D.WB;
+    const rows::TaskDerived d = rows::derive_task(r, holders, D.default_data_size, D.WB, x);
+    auto cmp = [&](bool on, int field, int64_t dev, int64_t expct, int64_t sub) {
+      report(A, on && dev != expct, DGP_AR_ROW_TASKS, field, t, sub, dev, expct);
+    };
+    const uint8_t tf = D.tflags[t], td = D.tdyn[t];
+    cmp(true, DGP_AF_STATE, D.state[t], s, -1);
+    cmp(true, DGP_AF_WAITERS, D.waiters[t], r.waiters, -1);
+    cmp(true, DGP_AF_PROC_ON, D.proc_on[t], r.proc_on, -1);
+    cmp(true, DGP_AF_RES_NBYTES, D.res_nbytes[t], r.nbytes, -1);
+    for (int b = 0; b < D.WB; b++)  // sub = the word
+      cmp(true, DGP_AF_WHO_HAS, (int64_t)D.holders[(size_t)t * D.WB + b], (int64_t)x[b], b);
+    cmp(true, DGP_AF_LR, td & TD_LR, d.tdyn & TD_LR, -1);
+    cmp(true, DGP_AF_WANTED, tf & TF_WANTED, rows::task_flag_bits(r) & TF_WANTED, -1);
+    cmp(true, DGP_AF_FORGOTTEN, tf & TF_FORGOTTEN, rows::task_flag_bits(r) & TF_FORGOTTEN, -1);
+    cmp(s == S_WAITING || s == S_PROCESSING || s == S_QUEUED || s == S_NO_WORKER, DGP_AF_REMAINING, D.remaining[t],
+        r.remaining, -1);
+    cmp(s == S_MEMORY, DGP_AF_CUR_NBYTES, D.cur_nbytes[t], d.cur_nbytes, -1);
+    cmp(s == S_PROCESSING || (s == S_MEMORY && r.hn == 1), DGP_AF_HOLDER_OF, D.holder_of[t], d.holder_of, -1);
+    cmp(r.hn > 1, DGP_AF_MULTI, td & TD_MULTI, d.tdyn & TD_MULTI, -1);
   }
 }
 

@@ -954,14 +954,8 @@ namespace ev {
 // ===================================================================== resync
 // After a stimulus the engine does not model, the scheduler decided it itself; the host then
 // hands over the scheduler's state (dgp_sync_*). Tasks: a sparse list of rows.
-struct SyncTask {
-  int32_t t, proc_on, remaining, waiters;
-  int64_t nbytes;  // TaskState.nbytes (raw: -1 = never reported)
-  int32_t hp, hn;  // who_has: holders [hp, hp + hn) of the holder list
-  uint8_t state, lr, pad0, pad1;
-  int32_t pad2;
-};
-static_assert(sizeof(SyncTask) == 40, "SyncTask layout is shared with the host");
+// The rows are normalised on the host (dgp_rows.h), which also holds what follows from a row.
+using SyncTask = rows::TaskRow;
 
 __global__ void k_sync_tasks(const Dev* __restrict__ Dp, const SyncTask* __restrict__ rows, int n,
                              const int32_t* __restrict__ holders) {
@@ -974,18 +968,13 @@ __global__ void k_sync_tasks(const Dev* __restrict__ Dp, const SyncTask* __restr
     D.waiters[t] = r.waiters;
     D.proc_on[t] = r.proc_on;
     D.res_nbytes[t] = r.nbytes;
-    D.cur_nbytes[t] = r.state == S_MEMORY ? nbv(D, r.nbytes) : -1;
     D.fr_mark[t] = -1;
     D.rel_mark[t] = -1;
-    for (int b = 0; b < D.WB; b++) D.holders[(size_t)t * D.WB + b] = 0;
-    int first = -1;
-    for (int k = 0; k < r.hn; k++) {
-      const int w = holders[r.hp + k];
-      D.holders[(size_t)t * D.WB + (w >> 6)] |= 1ull << (w & 63);
-      if (first < 0) first = w;
-    }
-    D.holder_of[t] = r.state == S_PROCESSING ? r.proc_on : first;
-    D.tdyn[t] = (uint8_t)((r.lr ? TD_LR : 0) | (r.hn > 1 ? TD_MULTI : 0));
+    const dgp::rows::TaskDerived d =
+        dgp::rows::derive_task(r, holders, D.default_data_size, D.WB, D.holders + (size_t)t * D.WB);
+    D.cur_nbytes[t] = d.cur_nbytes;
+    D.holder_of[t] = d.holder_of;
+    D.tdyn[t] = d.tdyn;
   }
 }
 

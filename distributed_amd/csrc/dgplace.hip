@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/dgplace.h"
+#include "dgp_rows.h"  // the resync rows, normalised once for dgp_sync_* and dgp_audit_*
 #include "dgp_device.h"
 #include "dgp_msgs.h"
 #include "dgp_stream.h"  // dgp::st: the 32-slot window with wait-in-place claims
@@ -368,6 +369,51 @@ int grid_for(int64_t n, int per_block, int cap) {
   return (int)b;
 }
 
+namespace rows = dgp::rows;
+static_assert(rows::PD == dgp::st::PD && rows::PMAX == dgp::PMAX && rows::PMAX_G == dgp::PMAX_G &&
+                  rows::NLW == dgp::st::NLW && rows::NXW == dgp::st::NXW,
+              "dgp_rows.h restates the device headers' layout");
+static_assert(rows::S_RELEASED == dgp::S_RELEASED && rows::S_PROCESSING == dgp::S_PROCESSING &&
+                  rows::S_MEMORY == dgp::S_MEMORY && rows::S_FORGOTTEN == dgp::S_ERRED + 1 &&
+                  rows::TF_WANTED == dgp::TF_WANTED && rows::TF_FORGOTTEN == dgp::TF_FORGOTTEN &&
+                  rows::WF_IDLE == dgp::WF_IDLE && rows::WF_SAT == dgp::WF_SAT && rows::WF_ITC == dgp::WF_ITC &&
+                  rows::WF_PAUSED == dgp::WF_PAUSED && rows::TD_LR == dgp::TD_LR && rows::TD_MULTI == dgp::TD_MULTI,
+              "dgp_rows.h restates the device headers' state and flag values");
+
+// what the row rules (dgp_rows.h) read of the engine
+rows::Shape row_shape(const dgp_engine* e) {
+  const dgp::Dev& D = e->D;
+  return rows::Shape{D.N, D.W, D.WB, D.P, D.G, D.saturation, D.sat_inf != 0, D.default_data_size,
+                     e->nthreads.data(), e->paused_h.data()};
+}
+
+// a worker's slot cap before its long-running tasks
+int32_t base_cap(const dgp::Dev& D, int32_t nthreads) { return rows::base_cap(D.saturation, D.sat_inf != 0, nthreads); }
+
+// is_rootish (:2929-2947) from the host mirrors: TaskState._rootish wins, else the group rule
+// for a task without restrictions
+bool task_rootish(const dgp_engine* e, int64_t t) {
+  if (e->rootish_override_h[t] >= 0) return e->rootish_override_h[t] != 0;
+  const int g = e->group_h[t];
+  return e->group_sizes[g] > e->D.total_nthreads * 2 && e->gdep_n[g] < 5 && e->gdep_len[g] < 5 &&
+         !(!e->restr_h.empty() && (e->restr_h[t] & dgp::RF_RESTRICTED));
+}
+
+uint8_t with_rootish(uint8_t tflags, bool rootish) {
+  return (uint8_t)((tflags & ~dgp::TF_ROOTISH) | (rootish ? dgp::TF_ROOTISH : 0));
+}
+
+// is_rootish reads total_nthreads: every task's flag follows a new total
+int refresh_rootish(dgp_engine* e, bool always_upload) {
+  std::vector<uint8_t> tf = e->tflags_h;
+  for (int64_t t = 0; t < e->D.N; t++) tf[t] = with_rootish(tf[t], task_rootish(e, t));
+  if (always_upload || tf != e->tflags_h) {
+    HIPCHK(e, hipMemcpy(const_cast<uint8_t*>(e->D.tflags), tf.data(), e->D.N, hipMemcpyHostToDevice));
+    e->tflags_h = tf;
+  }
+  return 0;
+}
+
 // run_id / holder_of of the placements the stream engine has not sequenced itself
 int set_runids(dgp_engine* e) {
   hipLaunchKernelGGL(dgp::svc::k_set_runids, dim3(64), dim3(256), 0, e->stream, e->d_dev);
@@ -703,8 +749,7 @@ int dgp_set_config(dgp_engine* e, int64_t bandwidth, int64_t default_data_size, 
   e->have_config = true;
   if (e->have_workers) {  // slot caps depend on the saturation (_task_slots_available :8765)
     std::vector<int32_t> cap(e->nthreads.size());
-    for (size_t w = 0; w < cap.size(); w++)
-      cap[w] = e->D.sat_inf ? 0 : std::max((int32_t)std::ceil(saturation * e->nthreads[w]), (int32_t)1);
+    for (size_t w = 0; w < cap.size(); w++) cap[w] = base_cap(e->D, e->nthreads[w]);
     HIPCHK(e, hipMemcpy(e->D.w_cap, cap.data(), cap.size() * 4, hipMemcpyHostToDevice));
   }
   return 0;
@@ -811,7 +856,8 @@ int upload_graph(dgp_engine* e, int64_t n_tasks, const int64_t* dep_ptr, const i
   for (int64_t t = 0; t < N; t++)
     for (int64_t k = dep_ptr[t]; k < dep_ptr[t + 1]; k++)
       if (prio[dep_idx[k]] >= prio[t]) return fail(e, DGP_E_ARG, "priorities must be topological");
-  // static is_rootish per group (:2929-2947; total_nthreads is fixed for the engine)
+  // static is_rootish per group (:2929-2947; total_nthreads is fixed for the engine); not
+  // task_rootish: the host mirrors it reads are filled from these arrays further down
   std::vector<int64_t> gsize(n_groups, 0);
   for (int64_t t = 0; t < N; t++) gsize[group_id[t]]++;
   std::vector<std::vector<int32_t>> gdeps(n_groups);
@@ -1005,6 +1051,7 @@ int dgp_set_restrictions(dgp_engine* e, const int64_t* restr_ptr, const int32_t*
           return fail(e, DGP_E_ARG, "dgp_set_restrictions: valid workers must ascend");
       }
       // is_rootish (:2929-2947): a restricted task is not root-ish unless _rootish says so
+      // (not task_rootish: restr_h takes these flags only once the whole call is good)
       if ((flags[t] & dgp::RF_RESTRICTED) && e->rootish_override_h[t] < 0) tf[t] &= (uint8_t)~dgp::TF_ROOTISH;
     }
   }
@@ -1109,13 +1156,7 @@ int dgp_update_restrictions(dgp_engine* e, int64_t n, const int32_t* task, const
     for (int64_t k = row_ptr[i]; k < row_ptr[i + 1]; k++) rows[q++] = row_idx[k];
     const int t = task[i];
     e->restr_h[t] = flags[i];
-    // is_rootish (:2929-2947): restrictions make a task non-root-ish unless _rootish says so
-    if (e->rootish_override_h[t] < 0) {
-      const int g = e->group_h[t];
-      const bool gr = e->group_sizes[g] > D.total_nthreads * 2 && e->gdep_n[g] < 5 && e->gdep_len[g] < 5;
-      const bool r = gr && !(flags[i] & dgp::RF_RESTRICTED);
-      tf[t] = (uint8_t)((tf[t] & ~dgp::TF_ROOTISH) | (r ? dgp::TF_ROOTISH : 0));
-    }
+    tf[t] = with_rootish(tf[t], task_rootish(e, t));  // restrictions make a task non-root-ish
   }
   HIPCHK(e, hipMemcpy(const_cast<int32_t*>(D.restr_pool) + e->rpool_used, rows.data(), add * 4, hipMemcpyHostToDevice));
   e->rpool_used += add;
@@ -1161,11 +1202,7 @@ int dgp_set_rootish(dgp_engine* e, int64_t n, const int32_t* task, const int8_t*
   for (int64_t i = 0; i < n; i++) {  // is_rootish (:2929-2947) with the new TaskState._rootish
     const int t = task[i];
     e->rootish_override_h[t] = value[i];
-    const int g = e->group_h[t];
-    const bool gr = e->group_sizes[g] > D.total_nthreads * 2 && e->gdep_n[g] < 5 && e->gdep_len[g] < 5;
-    const bool rs = !e->restr_h.empty() && (e->restr_h[t] & dgp::RF_RESTRICTED);
-    const bool r = value[i] >= 0 ? value[i] != 0 : (gr && !rs);
-    tf[t] = (uint8_t)((tf[t] & ~dgp::TF_ROOTISH) | (r ? dgp::TF_ROOTISH : 0));
+    tf[t] = with_rootish(tf[t], task_rootish(e, t));
   }
   if (tf != e->tflags_h) {
     HIPCHK(e, hipMemcpy(const_cast<uint8_t*>(D.tflags), tf.data(), D.N, hipMemcpyHostToDevice));
@@ -1789,26 +1826,10 @@ int dgp_add_worker_at(dgp_engine* e, int32_t nthreads, int32_t running, int32_t 
   e->paused_h.insert(e->paused_h.begin() + position, (uint8_t)(running ? 0 : 1));
   e->nthreads.insert(e->nthreads.begin() + pos, nthreads);
   D.total_nthreads += nthreads;
-  const int32_t cap = D.sat_inf ? 0 : std::max((int32_t)std::ceil(D.saturation * nthreads), (int32_t)1);
+  const int32_t cap = base_cap(D, nthreads);
   HIPCHK(e, hipMemcpy(D.w_nthreads + pos, &nthreads, 4, hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(D.w_cap + pos, &cap, 4, hipMemcpyHostToDevice));
-  // is_rootish (:2929-2947) reads total_nthreads: the groups' flags follow the new total
-  {
-    std::vector<uint8_t> tf = e->tflags_h;
-    bool changed = false;
-    for (int64_t t = 0; t < D.N; t++) {
-      const int g = e->group_h[t];
-      const bool gr = e->group_sizes[g] > D.total_nthreads * 2 && e->gdep_n[g] < 5 && e->gdep_len[g] < 5;
-      const bool rs = !e->restr_h.empty() && (e->restr_h[t] & dgp::RF_RESTRICTED);
-      const bool r = e->rootish_override_h[t] >= 0 ? e->rootish_override_h[t] != 0 : (gr && !rs);
-      tf[t] = (uint8_t)((tf[t] & ~dgp::TF_ROOTISH) | (r ? dgp::TF_ROOTISH : 0));
-      changed = changed || tf[t] != e->tflags_h[t];
-    }
-    if (changed) {
-      HIPCHK(e, hipMemcpy(const_cast<uint8_t*>(D.tflags), tf.data(), D.N, hipMemcpyHostToDevice));
-      e->tflags_h = tf;
-    }
-  }
+  if (int rc2 = refresh_rootish(e, false)) return rc2;  // the new total_nthreads
   e->mode = 2;
   if (int rc2 = grow_logs(e, 0)) return rc2;
   if (int rc2 = sync_dev(e)) return rc2;
@@ -1953,25 +1974,6 @@ int dgp_add_graph_deferred(dgp_engine* e, int64_t n_new, const int64_t* dep_ptr,
 
 namespace {
 int stage_args(dgp_engine* e, std::initializer_list<std::pair<const void*, size_t>> parts, std::vector<char*>& out);
-// is_rootish (:2929-2947) reads total_nthreads: the groups' flags follow a new total
-int refresh_rootish(dgp_engine* e) {
-  dgp::Dev& D = e->D;
-  std::vector<uint8_t> tf = e->tflags_h;
-  bool changed = false;
-  for (int64_t t = 0; t < D.N; t++) {
-    const int g = e->group_h[t];
-    const bool gr = e->group_sizes[g] > D.total_nthreads * 2 && e->gdep_n[g] < 5 && e->gdep_len[g] < 5;
-    const bool rs = !e->restr_h.empty() && (e->restr_h[t] & dgp::RF_RESTRICTED);
-    const bool r = e->rootish_override_h[t] >= 0 ? e->rootish_override_h[t] != 0 : (gr && !rs);
-    tf[t] = (uint8_t)((tf[t] & ~dgp::TF_ROOTISH) | (r ? dgp::TF_ROOTISH : 0));
-    changed = changed || tf[t] != e->tflags_h[t];
-  }
-  if (changed) {
-    HIPCHK(e, hipMemcpy(const_cast<uint8_t*>(D.tflags), tf.data(), D.N, hipMemcpyHostToDevice));
-    e->tflags_h = tf;
-  }
-  return 0;
-}
 // every earlier task a new one depends on gains it as a waiter (_transition_released_waiting
 // :2094-2099: dts.waiters.add(ts) for a dependency that is not released)
 __global__ void k_add_waiters(int32_t* waiters, const int32_t* dep, const int32_t* cnt, int64_t n) {
@@ -2270,10 +2272,8 @@ static int add_graph_impl(dgp_engine* e, int64_t n_new, const int64_t* dep_ptr, 
     D.restr_ptr = rpd;
     D.restr_idx = rid;
     D.restr_flags = rfd;
-    // a restricted task is not root-ish unless _rootish says so (is_rootish :2929-2947)
-    for (int64_t t = 0; t < N0; t++)
-      if ((e->restr_h[t] & dgp::RF_RESTRICTED) && e->rootish_override_h[t] < 0)
-        e->tflags_h[t] &= (uint8_t)~dgp::TF_ROOTISH;
+    // the upload's flags knew no restrictions; the mirrors do now
+    for (int64_t t = 0; t < N0; t++) e->tflags_h[t] = with_rootish(e->tflags_h[t], task_rootish(e, t));
   }
   HIPCHK(e, hipMemcpy(const_cast<uint8_t*>(D.tflags), e->tflags_h.data(), N1, hipMemcpyHostToDevice));
   free_list(old_allocs);
@@ -2563,7 +2563,7 @@ int dgp_remove_worker(dgp_engine* e, int32_t worker) {
     if (int rc = dgp_set_worker_status(e, worker, 0, &placed)) return rc;
   e->paused_h[worker] = 2;
   e->D.total_nthreads -= e->nthreads[worker];
-  return refresh_rootish(e);
+  return refresh_rootish(e, false);
 }
 
 // the order rows of dgp_lose_worker_ordered / dgp_graph_stimulus_ordered: sorted by (task,
@@ -2719,7 +2719,7 @@ int dgp_lose_worker_ordered(dgp_engine* e, int32_t worker, int64_t n_processing,
   e->paused_h[worker] = 2;
   D.total_nthreads -= e->nthreads[worker];
   D.evf |= dgp::EVF_PAUSED;
-  if (int rc = refresh_rootish(e)) return rc;
+  if (int rc = refresh_rootish(e, false)) return rc;
   HIPCHK(e, hipMemsetAsync(D.ready_key, 0xff, (size_t)D.N * 8, e->stream));  // the recommendation dict: empty
   std::vector<char*> a;
   const int64_t n_oidx = n_order ? order_ptr[n_order] : 0;
@@ -2781,58 +2781,33 @@ int dgp_sync_placements(dgp_engine* e, int64_t n, const int32_t* task, const int
   return 0;
 }
 
+// The resync. Each call is: readiness test, normalise the rows (dgp_rows.h), apply the image.
+// A refused call changes nothing: the host mirrors (paused_h, total_nthreads, tflags_h,
+// h_wanted, D.evf) follow only once the whole call is known to be good.
 int dgp_sync_tasks(dgp_engine* e, int64_t n, const int32_t* task, const uint8_t* state, const int32_t* remaining,
                    const int32_t* waiters, const int32_t* processing_on, const int64_t* nbytes,
                    const uint8_t* long_running, const uint8_t* wanted, const int64_t* holder_ptr,
                    const int32_t* holder_idx) {
   if (int rc_ = resident_stop(e)) return rc_;
   if (int rc = event_ready(e, "dgp_sync_tasks")) return rc;
-  if (n < 0 || (n > 0 && (!task || !state || !remaining || !waiters || !processing_on || !nbytes || !long_running ||
-                          !wanted || !holder_ptr)))
-    return fail(e, DGP_E_ARG, "dgp_sync_tasks: bad rows");
-  if (n == 0) return 0;
+  rows::TaskImage img;
+  if (const char* bad = rows::task_rows(row_shape(e), n, task, state, remaining, waiters, processing_on, nbytes,
+                                        long_running, wanted, holder_ptr, holder_idx, img))
+    return fail(e, DGP_E_ARG, std::string("dgp_sync_tasks: ") + bad);
+  if (img.rows.empty()) return 0;
   const dgp::Dev& D = e->D;
-  const int64_t H = holder_ptr[n];
-  if (holder_ptr[0] != 0 || H < 0 || (H > 0 && !holder_idx)) return fail(e, DGP_E_ARG, "dgp_sync_tasks: holder_ptr");
-  std::vector<dgp::ev::SyncTask> rows(n);
-  bool lr = false, multi = false;
-  for (int64_t i = 0; i < n; i++) {
-    const int32_t t = task[i];
-    if (t < 0 || t >= D.N || state[i] > dgp::S_ERRED + 1 || holder_ptr[i + 1] < holder_ptr[i])
-      return fail(e, DGP_E_ARG, "dgp_sync_tasks: task / state / holder_ptr");
-    if (state[i] == dgp::S_PROCESSING && (processing_on[i] < 0 || processing_on[i] >= D.W))
-      return fail(e, DGP_E_ARG, "dgp_sync_tasks: processing task without a worker");
-    for (int64_t k = holder_ptr[i]; k < holder_ptr[i + 1]; k++)
-      if (holder_idx[k] < 0 || holder_idx[k] >= D.W) return fail(e, DGP_E_ARG, "dgp_sync_tasks: holder out of range");
-    auto& r = rows[i];
-    r = dgp::ev::SyncTask{};
-    r.t = t;
-    r.proc_on = state[i] == dgp::S_PROCESSING ? processing_on[i] : -1;
-    r.remaining = remaining[i];
-    r.waiters = waiters[i];
-    r.nbytes = nbytes[i];
-    r.hp = (int32_t)holder_ptr[i];
-    r.hn = (int32_t)(holder_ptr[i + 1] - holder_ptr[i]);
-    // state 7 = forgotten (:2853): the row stays, released, flagged so that nothing walks it as
-    // a dependent any more (_propagate_forgotten drops it from its dependencies' dependents)
-    const bool forgotten = state[i] == dgp::S_ERRED + 1;
-    r.state = forgotten ? (uint8_t)dgp::S_RELEASED : state[i];
-    r.lr = long_running[i] ? 1 : 0;
-    lr = lr || r.lr;
-    multi = multi || r.hn > 1;
-    // who_wants (TF_WANTED) rides on the host copy of the task flags
-    e->tflags_h[t] = (uint8_t)((e->tflags_h[t] & ~(dgp::TF_WANTED | dgp::TF_FORGOTTEN)) |
-                               (wanted[i] ? dgp::TF_WANTED : 0) | (forgotten ? dgp::TF_FORGOTTEN : 0));
-    e->h_wanted[t] = wanted[i] ? 1 : 0;
+  for (const rows::TaskRow& r : img.rows) {
+    e->tflags_h[r.t] = (uint8_t)((e->tflags_h[r.t] & ~(dgp::TF_WANTED | dgp::TF_FORGOTTEN)) | rows::task_flag_bits(r));
+    e->h_wanted[r.t] = r.wanted;
   }
   HIPCHK(e, hipStreamSynchronize(e->stream));
   HIPCHK(e, hipMemcpy(const_cast<uint8_t*>(D.tflags), e->tflags_h.data(), D.N, hipMemcpyHostToDevice));
   std::vector<char*> a;
-  if (int rc = stage_args(e, {{rows.data(), rows.size() * sizeof(dgp::ev::SyncTask)}, {holder_idx, (size_t)H * 4}}, a))
+  if (int rc = stage_args(e, {{img.rows.data(), img.rows.size() * sizeof(rows::TaskRow)},
+                              {holder_idx, (size_t)holder_ptr[n] * 4}}, a))
     return rc;
   // every resync may leave replica rows and long-running tasks: the paths that honour them stay on
-  e->D.evf |= dgp::EVF_MULTI | (lr ? dgp::EVF_LR : 0);
-  (void)multi;
+  e->D.evf |= dgp::EVF_MULTI | (img.lr_any ? dgp::EVF_LR : 0);
   if (int rc = sync_dev(e)) return rc;
   hipLaunchKernelGGL(dgp::ev::k_sync_tasks, dim3(grid_for(n, 256, 1024)), dim3(256), 0, e->stream, e->d_dev,
                      (const dgp::ev::SyncTask*)a[0], (int)n, (const int32_t*)a[1]);
@@ -2846,99 +2821,53 @@ int dgp_sync_workers(dgp_engine* e, int32_t n_workers, const int8_t* status, con
                      const int64_t* needs_ptr, const int32_t* needs_task, const int32_t* needs_count) {
   if (int rc_ = resident_stop(e)) return rc_;
   if (int rc = event_ready(e, "dgp_sync_workers")) return rc;
+  rows::WorkerImage img;
+  if (const char* bad = rows::worker_rows(row_shape(e), n_workers, status, nproc, n_long_running, plen, prefix, count,
+                                          netocc, nbytes, idle, saturated, needs_ptr, needs_task, needs_count, img))
+    return fail(e, DGP_E_ARG, std::string("dgp_sync_workers: ") + bad);
   dgp::Dev& D = e->D;
   namespace S = dgp::st;
   const int W = D.W;
-  if (n_workers != W || !status || !nproc || !n_long_running || !plen || !prefix || !count || !netocc || !nbytes ||
-      !idle || !saturated || !needs_ptr)
-    return fail(e, DGP_E_ARG, "dgp_sync_workers: one row per engine worker");
-  std::vector<int32_t> cap(W), pf((size_t)W * dgp::PMAX, 0), pc((size_t)W * dgp::PMAX, 0), pl(W);
-  std::vector<uint8_t> fl(W);
-  std::vector<int64_t> slots(W, 0);
+  // needs_what in the engine's layout: up to NLW - 1 entries in the line, then NXW overflow
+  // entries, then scan mode
   std::vector<uint32_t> lines((size_t)W * S::NLW, 0), ext((size_t)W * S::NXW, 0);
-  int64_t n_idle = 0, n_sat = 0, n_itc = 0, itc_slots = 0;
-  bool paused_any = false, lr_any = false;
   for (int w = 0; w < W; w++) {
-    if (status[w] < 0 || status[w] > 2) return fail(e, DGP_E_ARG, "dgp_sync_workers: status");
-    if (plen[w] < 0 || plen[w] > S::PD) return fail(e, DGP_E_ARG, "dgp_sync_workers: more than 8 prefixes on a worker");
-    const bool running = status[w] == 0;
-    if (!running && (idle[w] || saturated[w]))
-      return fail(e, DGP_E_ARG, "dgp_sync_workers: a worker that is not running is neither idle nor saturated");
-    if (status[w] == 2 && e->paused_h[w] != 2) D.total_nthreads -= e->nthreads[w];  // removed (:5217)
-    if (status[w] != 2 && e->paused_h[w] == 2) return fail(e, DGP_E_ARG, "dgp_sync_workers: a removed worker returns");
-    e->paused_h[w] = (uint8_t)status[w];
-    paused_any = paused_any || !running;
-    lr_any = lr_any || n_long_running[w] > 0;
-    const int32_t nt = std::max<int32_t>(e->nthreads[w], 1);
-    const int32_t base = D.sat_inf ? 0 : std::max((int32_t)std::ceil(D.saturation * nt), (int32_t)1);
-    cap[w] = base + (D.sat_inf ? 0 : n_long_running[w]);
-    pl[w] = plen[w];
-    for (int i = 0; i < plen[w]; i++) {
-      if (prefix[(size_t)w * S::PD + i] < 0 || prefix[(size_t)w * S::PD + i] >= D.P)
-        return fail(e, DGP_E_ARG, "dgp_sync_workers: prefix id");
-      pf[(size_t)w * dgp::PMAX + i] = prefix[(size_t)w * S::PD + i];
-      pc[(size_t)w * dgp::PMAX + i] = count[(size_t)w * S::PD + i];
-    }
-    const bool itc = running && (D.sat_inf || cap[w] - nproc[w] > 0);
-    fl[w] = (uint8_t)((idle[w] ? dgp::WF_IDLE : 0) | (saturated[w] ? dgp::WF_SAT : 0) | (itc ? dgp::WF_ITC : 0) |
-                      (running ? 0 : dgp::WF_PAUSED));
-    slots[w] = itc && !D.sat_inf ? cap[w] - nproc[w] : 0;
-    n_idle += idle[w] ? 1 : 0;
-    n_sat += saturated[w] ? 1 : 0;
-    n_itc += itc ? 1 : 0;
-    itc_slots += slots[w];
-    // needs_what: up to NLW - 1 entries in the line, then NXW overflow entries, then scan mode
-    const int64_t k0 = needs_ptr[w], k1 = needs_ptr[w + 1];
-    const int64_t m = k1 - k0;
-    if (k1 < k0 || (m > 0 && (!needs_task || !needs_count))) return fail(e, DGP_E_ARG, "dgp_sync_workers: needs_ptr");
+    const int64_t k0 = img.needs_ptr[w], m = img.needs_ptr[w + 1] - k0;
     uint32_t* L = lines.data() + (size_t)w * S::NLW;
-    if (m > (S::NLW - 1) + S::NXW) {
+    if (rows::scan_mode(m)) {
       L[S::NLW - 1] = S::NL_OVF;
-    } else {
-      for (int64_t k = 0; k < m; k++) {
-        const int32_t d = needs_task[k0 + k], c = needs_count[k0 + k];
-        if (d < 0 || d >= D.N || c <= 0 || c > 255) return fail(e, DGP_E_ARG, "dgp_sync_workers: needs_what entry");
-        const uint32_t v = ((uint32_t)d << 8) | (uint32_t)c;
-        if (k < S::NLW - 1) L[k] = v;
-        else ext[(size_t)w * S::NXW + (k - (S::NLW - 1))] = v;
-      }
-      L[S::NLW - 1] = ((uint32_t)m << 8) | (m > S::NLW - 1 ? 1u : 0u);
+      continue;
     }
+    for (int64_t k = 0; k < m; k++)
+      (k < S::NLW - 1 ? L[k] : ext[(size_t)w * S::NXW + (k - (S::NLW - 1))]) = img.needs[k0 + k];
+    L[S::NLW - 1] = ((uint32_t)m << 8) | (m > S::NLW - 1 ? 1u : 0u);
   }
-  // is_rootish (:2929-2947) follows total_nthreads
-  {
-    std::vector<uint8_t>& tf = e->tflags_h;
-    for (int64_t t = 0; t < D.N; t++) {
-      const int g = e->group_h[t];
-      const bool gr = e->group_sizes[g] > D.total_nthreads * 2 && e->gdep_n[g] < 5 && e->gdep_len[g] < 5;
-      const bool rs = !e->restr_h.empty() && (e->restr_h[t] & dgp::RF_RESTRICTED);
-      const bool r = e->rootish_override_h[t] >= 0 ? e->rootish_override_h[t] != 0 : (gr && !rs);
-      tf[t] = (uint8_t)((tf[t] & ~dgp::TF_ROOTISH) | (r ? dgp::TF_ROOTISH : 0));
-    }
-  }
+  for (int w = 0; w < W; w++)
+    if (img.status[w] == 2 && e->paused_h[w] != 2) D.total_nthreads -= e->nthreads[w];  // removed (:5217)
+  e->paused_h = img.status;
   HIPCHK(e, hipStreamSynchronize(e->stream));
-  HIPCHK(e, hipMemcpy(const_cast<uint8_t*>(D.tflags), e->tflags_h.data(), D.N, hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(D.w_cap, cap.data(), (size_t)W * 4, hipMemcpyHostToDevice));
+  if (int rc = refresh_rootish(e, true)) return rc;  // is_rootish follows total_nthreads
+  HIPCHK(e, hipMemcpy(D.w_cap, img.cap.data(), (size_t)W * 4, hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(D.w_nproc, nproc, (size_t)W * 4, hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(D.w_plen, pl.data(), (size_t)W * 4, hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(D.w_pfx, pf.data(), pf.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(D.w_pcnt, pc.data(), pc.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(D.w_plen, img.plen.data(), (size_t)W * 4, hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(D.w_pfx, img.pfx.data(), img.pfx.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(D.w_pcnt, img.pcnt.data(), img.pcnt.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(D.w_netocc, netocc, (size_t)W * 8, hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(D.w_nbytes, nbytes, (size_t)W * 8, hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(D.w_flags, fl.data(), (size_t)W, hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(D.w_itcslots, slots.data(), (size_t)W * 8, hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(D.w_flags, img.flags.data(), (size_t)W, hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(D.w_itcslots, img.slots.data(), (size_t)W * 8, hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(D.gw_needs_saved, lines.data(), lines.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(D.gw_needs_ext, ext.data(), ext.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(D.w_nthreads, e->nthreads.data(), (size_t)W * 4, hipMemcpyHostToDevice));
   dgp::Ctl c;
   if (int rc = read_ctl(e, &c)) return rc;
-  c.n_idle = n_idle;
-  c.n_sat = n_sat;
-  c.n_itc = n_itc;
-  c.itc_slots = itc_slots;
+  c.n_idle = img.tot[0];
+  c.n_sat = img.tot[1];
+  c.n_itc = img.tot[2];
+  c.itc_slots = img.tot[3];
   HIPCHK(e, hipMemcpy(e->ctl, &c, sizeof c, hipMemcpyHostToDevice));
-  if (paused_any) D.evf |= dgp::EVF_PAUSED;
-  if (lr_any) D.evf |= dgp::EVF_LR;
+  if (img.paused_any) D.evf |= dgp::EVF_PAUSED;
+  if (img.lr_any) D.evf |= dgp::EVF_LR;
   return sync_dev(e);
 }
 
@@ -2948,17 +2877,11 @@ int dgp_sync_globals(dgp_engine* e, int64_t n_tasks_counter, double network_occ_
                      const int64_t* group_released_waiting, const int64_t* group_left, const int32_t* group_last_worker) {
   if (int rc_ = resident_stop(e)) return rc_;
   if (int rc = event_ready(e, "dgp_sync_globals")) return rc;
+  if (const char* bad = rows::global_rows(row_shape(e), g_plen, g_prefix, g_count, n_queued, queued, duration_average,
+                                          max_exec_time, bandwidth, group_released_waiting, group_left,
+                                          group_last_worker))
+    return fail(e, DGP_E_ARG, std::string("dgp_sync_globals: ") + bad);
   dgp::Dev& D = e->D;
-  if (g_plen < 0 || g_plen > dgp::PMAX_G || (g_plen > 0 && (!g_prefix || !g_count)) || n_queued < 0 ||
-      n_queued > D.N || (n_queued > 0 && !queued) || !duration_average || !max_exec_time || !(bandwidth > 0) ||
-      !group_released_waiting || !group_left || !group_last_worker)
-    return fail(e, DGP_E_ARG, "dgp_sync_globals: bad arguments");
-  for (int i = 0; i < g_plen; i++)
-    if (g_prefix[i] < 0 || g_prefix[i] >= D.P) return fail(e, DGP_E_ARG, "dgp_sync_globals: prefix id");
-  for (int64_t i = 0; i < n_queued; i++)
-    if (queued[i] < 0 || queued[i] >= D.N) return fail(e, DGP_E_ARG, "dgp_sync_globals: queued task");
-  for (int g = 0; g < D.G; g++)
-    if (group_last_worker[g] < -1 || group_last_worker[g] >= D.W) return fail(e, DGP_E_ARG, "dgp_sync_globals: last worker");
   HIPCHK(e, hipStreamSynchronize(e->stream));
   dgp::Ctl c;
   if (int rc = read_ctl(e, &c)) return rc;
@@ -2992,26 +2915,156 @@ int dgp_sync_globals(dgp_engine* e, int64_t n_tasks_counter, double network_occ_
   return 0;
 }
 
+}  // extern "C"
+
+namespace {
+
 // The state audit (include/dgplace.h, dgp_audit.h). Nothing of the engine changes: the
-// readiness test is event_ready's without its mode switch, the recount lives in an arena of
-// its own, and the only host fields touched are that arena's pointer and size.
-int dgp_audit_state(dgp_engine* e, int64_t cap, dgp_violation* out, int64_t* n_violations, int64_t* n_skipped) {
-  if (int rc_ = resident_stop(e)) return rc_;
+// recount lives in an arena of its own, and the only host fields touched are that arena's
+// pointer and size.
+
+// event_ready without its mode switch. A pending resync refuses the state audit (the state is
+// the scheduler's to hand over) and not the row audits (that is when the rows arrive).
+int audit_ready(dgp_engine* e, const char* what, bool state_audit, int64_t cap, dgp_violation* out,
+                int64_t* n_violations) {
   if (!e) return DGP_E_ARG;
   if (n_violations) *n_violations = 0;
-  if (n_skipped) *n_skipped = 0;
-  if (cap < 0 || (cap > 0 && !out) || !n_violations) return fail(e, DGP_E_ARG, "dgp_audit_state: bad output arguments");
+  if (cap < 0 || (cap > 0 && !out) || !n_violations) return fail(e, DGP_E_ARG, std::string(what) + ": bad output arguments");
   if (!e->graph_done) return fail(e, DGP_E_STATE, "dgp_update_graph first");
-  if (e->pending_resync)
-    return fail(e, DGP_E_STATE, "dgp_audit_state: a resync is pending (the state is the scheduler's to hand over)");
+  if (state_audit && e->pending_resync)
+    return fail(e, DGP_E_STATE, std::string(what) + ": a resync is pending (the state is the scheduler's to hand over)");
   if (e->mode == 1)
-    return fail(e, DGP_E_STATE, "dgp_audit_state: engine advanced by a replay (dgp_run_rounds): its state is not "
-                                "canonical between rounds");
-  const dgp::Dev& D = e->D;
-  if (!(D.P <= dgp::st::PX) || !D.gw_needs_saved)
-    return fail(e, DGP_E_STATE, "dgp_audit_state: the round-kernel engine (more than 32 prefixes) has no state audit");
-  namespace AU = dgp::audit;
+    return fail(e, DGP_E_STATE, state_audit ? std::string(what) + ": engine advanced by a replay (dgp_run_rounds): its "
+                                                                  "state is not canonical between rounds"
+                                            : "engine advanced by a replay (dgp_run_rounds); dgp_reset first");
+  if (!(e->D.P <= dgp::st::PX) || !e->D.gw_needs_saved)
+    return fail(e, DGP_E_STATE, std::string(what) + ": the round-kernel engine (more than 32 prefixes) has no state audit");
   HIPCHK(e, hipSetDevice(e->device));
+  return 0;
+}
+
+// the audits' device arena: grown when a call needs more, else reused
+int audit_arena(dgp_engine* e, size_t bytes) {
+  if (bytes <= e->d_audit_cap) return 0;
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (e->d_audit) (void)hipFree(e->d_audit);
+  e->d_audit = nullptr;
+  e->d_audit_cap = 0;
+  HIPCHK(e, hipMalloc((void**)&e->d_audit, bytes));
+  e->d_audit_cap = bytes;
+  return 0;
+}
+
+// the order every audit reports its records in
+void sort_violations(dgp_violation* out, int64_t n) {
+  std::sort(out, out + n, [](const dgp_violation& a, const dgp_violation& b) {
+    if (a.rule != b.rule) return a.rule < b.rule;
+    if (a.field != b.field) return a.field < b.field;
+    if (a.index != b.index) return a.index < b.index;
+    if (a.sub != b.sub) return a.sub < b.sub;
+    if (a.device_value != b.device_value) return a.device_value < b.device_value;
+    return a.expected_value < b.expected_value;
+  });
+}
+
+// One dgp_audit_tasks / _workers / _globals call: the arrays the resync would write are
+// staged in one blob, each with the device array it is compared against (k_au_cmp), plus the
+// queue / needs_what comparisons and what only the host holds.
+struct RowAudit {
+  static constexpr size_t NONE = ~(size_t)0;
+  struct Job {
+    int kind;  // 0 k_au_cmp, 1 k_au_row_queue, 2 k_au_row_needs, 3 k_au_row_tasks
+    const void* dev;
+    size_t expect, idx, lim_exp;
+    long long n;
+    int div, esz, rule, field, sub;
+    uint64_t mask;
+    const int32_t* lim_dev;
+  };
+  std::vector<char> blob;
+  std::vector<Job> jobs;
+  std::vector<dgp_violation> host;  // fields the engine keeps on the host
+  size_t put(const void* p, size_t bytes) {
+    const size_t o = blob.size();
+    blob.resize(o + ((bytes + 15) & ~(size_t)15));
+    if (bytes && p) memcpy(blob.data() + o, p, bytes);  // (no p: zeroed scratch)
+    return o;
+  }
+  void cmp(const void* dev, const void* expect, long long n, int esz, int rule, int field, size_t idx = NONE,
+           int div = 1, uint64_t mask = ~0ull, int sub = -1, const int32_t* lim_dev = nullptr, size_t lim_exp = NONE) {
+    if (n <= 0) return;
+    jobs.push_back(Job{0, dev, put(expect, (size_t)n * esz), idx, lim_exp, n, div, esz, rule, field, sub, mask, lim_dev});
+  }
+};
+
+int row_audit_run(dgp_engine* e, RowAudit& R, int64_t cap, dgp_violation* out, int64_t* n_violations) {
+  namespace AU = dgp::audit;
+  const size_t o_out = 16, o_blob = o_out + (((size_t)cap * sizeof(dgp_violation) + 15) & ~(size_t)15);
+  if (int rc = audit_arena(e, o_blob + R.blob.size() + 16)) return rc;
+  char* B = e->d_audit;
+  AU::Scratch A{};
+  A.n_viol = (unsigned long long*)B;
+  A.out = (dgp_violation*)(B + o_out);
+  A.cap = cap;
+  if (int rc = sync_dev(e)) return rc;
+  HIPCHK(e, hipMemsetAsync(B, 0, 16, e->stream));
+  if (!R.blob.empty())
+    HIPCHK(e, hipMemcpyAsync(B + o_blob, R.blob.data(), R.blob.size(), hipMemcpyHostToDevice, e->stream));
+  const dim3 blk(256);
+  for (const RowAudit::Job& j : R.jobs) {
+    const char* x = B + o_blob + j.expect;
+    const int32_t* idx = j.idx == RowAudit::NONE ? nullptr : (const int32_t*)(B + o_blob + j.idx);
+    const int32_t* le = j.lim_exp == RowAudit::NONE ? nullptr : (const int32_t*)(B + o_blob + j.lim_exp);
+    const dim3 grid(grid_for(j.n, 256, 2048));
+    if (j.kind == 1)
+      hipLaunchKernelGGL(AU::k_au_row_queue, grid, blk, 0, e->stream, e->d_dev, (const int32_t*)x, j.n, A);
+    else if (j.kind == 2)
+      hipLaunchKernelGGL(AU::k_au_row_needs, dim3(grid_for((int64_t)e->D.W * 64, 256, 2048)), blk, 0, e->stream, e->d_dev,
+                         (const int64_t*)x, (const uint32_t*)(B + o_blob + j.idx), A);
+    else if (j.kind == 3)
+      hipLaunchKernelGGL(AU::k_au_row_tasks, grid, blk, 0, e->stream, e->d_dev, (const rows::TaskRow*)x, j.n, idx,
+                         (unsigned long long*)(B + o_blob + j.lim_exp), A);
+    else if (j.esz == 1)
+      hipLaunchKernelGGL(AU::k_au_cmp<uint8_t>, grid, blk, 0, e->stream, (const uint8_t*)j.dev, (const uint8_t*)x, idx, j.n,
+                         j.div, (uint8_t)j.mask, j.rule, j.field, j.sub, j.lim_dev, le, A);
+    else if (j.esz == 4)
+      hipLaunchKernelGGL(AU::k_au_cmp<int32_t>, grid, blk, 0, e->stream, (const int32_t*)j.dev, (const int32_t*)x, idx, j.n,
+                         j.div, (int32_t)j.mask, j.rule, j.field, j.sub, j.lim_dev, le, A);
+    else
+      hipLaunchKernelGGL(AU::k_au_cmp<int64_t>, grid, blk, 0, e->stream, (const int64_t*)j.dev, (const int64_t*)x, idx, j.n,
+                         j.div, (int64_t)j.mask, j.rule, j.field, j.sub, j.lim_dev, le, A);
+  }
+  HIPCHK(e, hipGetLastError());
+  unsigned long long total = 0;
+  HIPCHK(e, hipMemcpyAsync(&total, A.n_viol, 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  int64_t kept = (int64_t)std::min<unsigned long long>(total, (unsigned long long)cap);
+  if (kept) HIPCHK(e, hipMemcpy(out, A.out, (size_t)kept * sizeof(dgp_violation), hipMemcpyDeviceToHost));
+  for (const dgp_violation& v : R.host) {
+    if (kept < cap) out[kept++] = v;
+    total++;
+  }
+  sort_violations(out, kept);
+  *n_violations = (int64_t)total;
+  return 0;
+}
+
+int64_t dbits(double x) {
+  int64_t v;
+  memcpy(&v, &x, 8);
+  return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dgp_audit_state(dgp_engine* e, int64_t cap, dgp_violation* out, int64_t* n_violations, int64_t* n_skipped) {
+  if (int rc_ = resident_stop(e)) return rc_;
+  if (e && n_skipped) *n_skipped = 0;
+  if (int rc = audit_ready(e, "dgp_audit_state", true, cap, out, n_violations)) return rc;
+  const dgp::Dev& D = e->D;
+  namespace AU = dgp::audit;
   const size_t N = (size_t)D.N, W = (size_t)D.W, P = (size_t)D.P, G = (size_t)D.G;
   // the arena: [zeroed counters | host inputs | violation records], each part 16-byte aligned
   size_t off = 0;
@@ -3025,14 +3078,7 @@ int dgp_audit_state(dgp_engine* e, int64_t cap, dgp_violation* out, int64_t* n_v
                o_gsum = take(P * 8), o_tot = take(8 * 8), o_scan = take(W), o_nviol = take(8);
   const size_t zero_bytes = off;
   const size_t o_status = take(W), o_bcap = take(W * 4), o_out = take((size_t)cap * sizeof(dgp_violation));
-  if (off > e->d_audit_cap) {
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (e->d_audit) (void)hipFree(e->d_audit);
-    e->d_audit = nullptr;
-    e->d_audit_cap = 0;
-    HIPCHK(e, hipMalloc((void**)&e->d_audit, off));
-    e->d_audit_cap = off;
-  }
+  if (int rc = audit_arena(e, off)) return rc;
   char* B = e->d_audit;
   AU::Scratch A{};
   A.c_nproc = (int32_t*)(B + o_nproc);
@@ -3052,10 +3098,7 @@ int dgp_audit_state(dgp_engine* e, int64_t cap, dgp_violation* out, int64_t* n_v
   A.out = (dgp_violation*)(B + o_out);
   A.cap = cap;
   std::vector<int32_t> bcap(W);
-  for (size_t w = 0; w < W; w++) {  // the cap rule of dgp_sync_workers
-    const int32_t nt = std::max<int32_t>(e->nthreads[w], 1);
-    bcap[w] = D.sat_inf ? 0 : std::max((int32_t)std::ceil(D.saturation * nt), (int32_t)1);
-  }
+  for (size_t w = 0; w < W; w++) bcap[w] = base_cap(D, e->nthreads[w]);
   if (int rc = sync_dev(e)) return rc;
   HIPCHK(e, hipMemsetAsync(B, 0, zero_bytes, e->stream));
   HIPCHK(e, hipMemcpyAsync(B + o_status, e->paused_h.data(), W, hipMemcpyHostToDevice, e->stream));
@@ -3081,222 +3124,32 @@ int dgp_audit_state(dgp_engine* e, int64_t cap, dgp_violation* out, int64_t* n_v
   HIPCHK(e, hipMemcpyAsync(tot, A.c_tot, sizeof tot, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   const int64_t kept = (int64_t)std::min<unsigned long long>(total, (unsigned long long)cap);
-  if (kept) {
-    HIPCHK(e, hipMemcpy(out, A.out, (size_t)kept * sizeof(dgp_violation), hipMemcpyDeviceToHost));
-    std::sort(out, out + kept, [](const dgp_violation& a, const dgp_violation& b) {
-      if (a.rule != b.rule) return a.rule < b.rule;
-      if (a.field != b.field) return a.field < b.field;
-      if (a.index != b.index) return a.index < b.index;
-      if (a.sub != b.sub) return a.sub < b.sub;
-      if (a.device_value != b.device_value) return a.device_value < b.device_value;
-      return a.expected_value < b.expected_value;
-    });
-  }
+  if (kept) HIPCHK(e, hipMemcpy(out, A.out, (size_t)kept * sizeof(dgp_violation), hipMemcpyDeviceToHost));
+  sort_violations(out, kept);
   *n_violations = (int64_t)total;
   if (n_skipped) *n_skipped = tot[4];
   return 0;
 }
 
-}  // extern "C"
-
-namespace {
-
-// One dgp_audit_tasks / _workers / _globals call: the arrays the resync would write are
-// staged in one blob, each with the device array it is compared against (k_au_cmp), plus the
-// queue / needs_what comparisons and what only the host holds.
-struct RowAudit {
-  static constexpr size_t NONE = ~(size_t)0;
-  struct Job {
-    int kind;  // 0 k_au_cmp, 1 k_au_row_queue, 2 k_au_row_needs
-    const void* dev;
-    size_t expect, idx, lim_exp;
-    long long n;
-    int div, esz, rule, field, sub;
-    uint64_t mask;
-    const int32_t* lim_dev;
-  };
-  std::vector<char> blob;
-  std::vector<Job> jobs;
-  std::vector<dgp_violation> host;  // fields the engine keeps on the host
-  size_t put(const void* p, size_t bytes) {
-    const size_t o = blob.size();
-    blob.resize(o + ((bytes + 15) & ~(size_t)15));
-    if (bytes) memcpy(blob.data() + o, p, bytes);
-    return o;
-  }
-  void cmp(const void* dev, const void* expect, long long n, int esz, int rule, int field, size_t idx = NONE,
-           int div = 1, uint64_t mask = ~0ull, int sub = -1, const int32_t* lim_dev = nullptr, size_t lim_exp = NONE) {
-    if (n <= 0) return;
-    jobs.push_back(Job{0, dev, put(expect, (size_t)n * esz), idx, lim_exp, n, div, esz, rule, field, sub, mask, lim_dev});
-  }
-};
-
-// event_ready without its mode switch (the audits change nothing); a pending resync is when
-// the rows arrive, so it does not refuse
-int row_audit_ready(dgp_engine* e, const char* what, int64_t cap, dgp_violation* out, int64_t* n_violations) {
-  if (!e) return DGP_E_ARG;
-  if (n_violations) *n_violations = 0;
-  if (cap < 0 || (cap > 0 && !out) || !n_violations) return fail(e, DGP_E_ARG, std::string(what) + ": bad output arguments");
-  if (!e->graph_done) return fail(e, DGP_E_STATE, "dgp_update_graph first");
-  if (e->mode == 1) return fail(e, DGP_E_STATE, "engine advanced by a replay (dgp_run_rounds); dgp_reset first");
-  if (!(e->D.P <= dgp::st::PX) || !e->D.gw_needs_saved)
-    return fail(e, DGP_E_STATE, std::string(what) + ": the round-kernel engine (more than 32 prefixes) has no state audit");
-  HIPCHK(e, hipSetDevice(e->device));
-  return 0;
-}
-
-int row_audit_run(dgp_engine* e, RowAudit& R, int64_t cap, dgp_violation* out, int64_t* n_violations) {
-  namespace AU = dgp::audit;
-  const size_t o_out = 16, o_blob = o_out + (((size_t)cap * sizeof(dgp_violation) + 15) & ~(size_t)15);
-  const size_t need = o_blob + R.blob.size() + 16;
-  if (need > e->d_audit_cap) {
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (e->d_audit) (void)hipFree(e->d_audit);
-    e->d_audit = nullptr;
-    e->d_audit_cap = 0;
-    HIPCHK(e, hipMalloc((void**)&e->d_audit, need));
-    e->d_audit_cap = need;
-  }
-  char* B = e->d_audit;
-  AU::Scratch A{};
-  A.n_viol = (unsigned long long*)B;
-  A.out = (dgp_violation*)(B + o_out);
-  A.cap = cap;
-  if (int rc = sync_dev(e)) return rc;
-  HIPCHK(e, hipMemsetAsync(B, 0, 16, e->stream));
-  if (!R.blob.empty())
-    HIPCHK(e, hipMemcpyAsync(B + o_blob, R.blob.data(), R.blob.size(), hipMemcpyHostToDevice, e->stream));
-  const dim3 blk(256);
-  for (const RowAudit::Job& j : R.jobs) {
-    const char* x = B + o_blob + j.expect;
-    const int32_t* idx = j.idx == RowAudit::NONE ? nullptr : (const int32_t*)(B + o_blob + j.idx);
-    const int32_t* le = j.lim_exp == RowAudit::NONE ? nullptr : (const int32_t*)(B + o_blob + j.lim_exp);
-    const dim3 grid(grid_for(j.n, 256, 2048));
-    if (j.kind == 1)
-      hipLaunchKernelGGL(AU::k_au_row_queue, grid, blk, 0, e->stream, e->d_dev, (const int32_t*)x, j.n, A);
-    else if (j.kind == 2)
-      hipLaunchKernelGGL(AU::k_au_row_needs, dim3(grid_for((int64_t)e->D.W * 64, 256, 2048)), blk, 0, e->stream, e->d_dev,
-                         (const int64_t*)x, (const uint32_t*)(B + o_blob + j.idx), A);
-    else if (j.esz == 1)
-      hipLaunchKernelGGL(AU::k_au_cmp<uint8_t>, grid, blk, 0, e->stream, (const uint8_t*)j.dev, (const uint8_t*)x, idx, j.n,
-                         j.div, (uint8_t)j.mask, j.rule, j.field, j.sub, j.lim_dev, le, A);
-    else if (j.esz == 4)
-      hipLaunchKernelGGL(AU::k_au_cmp<int32_t>, grid, blk, 0, e->stream, (const int32_t*)j.dev, (const int32_t*)x, idx, j.n,
-                         j.div, (int32_t)j.mask, j.rule, j.field, j.sub, j.lim_dev, le, A);
-    else
-      hipLaunchKernelGGL(AU::k_au_cmp<int64_t>, grid, blk, 0, e->stream, (const int64_t*)j.dev, (const int64_t*)x, idx, j.n,
-                         j.div, (int64_t)j.mask, j.rule, j.field, j.sub, j.lim_dev, le, A);
-  }
-  HIPCHK(e, hipGetLastError());
-  unsigned long long total = 0;
-  HIPCHK(e, hipMemcpyAsync(&total, A.n_viol, 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  int64_t kept = (int64_t)std::min<unsigned long long>(total, (unsigned long long)cap);
-  if (kept) HIPCHK(e, hipMemcpy(out, A.out, (size_t)kept * sizeof(dgp_violation), hipMemcpyDeviceToHost));
-  for (const dgp_violation& v : R.host) {
-    if (kept < cap) out[kept++] = v;
-    total++;
-  }
-  std::sort(out, out + kept, [](const dgp_violation& a, const dgp_violation& b) {
-    if (a.rule != b.rule) return a.rule < b.rule;
-    if (a.field != b.field) return a.field < b.field;
-    if (a.index != b.index) return a.index < b.index;
-    if (a.sub != b.sub) return a.sub < b.sub;
-    if (a.device_value != b.device_value) return a.device_value < b.device_value;
-    return a.expected_value < b.expected_value;
-  });
-  *n_violations = (int64_t)total;
-  return 0;
-}
-
-int64_t dbits(double x) {
-  int64_t v;
-  memcpy(&v, &x, 8);
-  return v;
-}
-
-}  // namespace
-
-extern "C" {
-
+// The row audits. Each call is: readiness test, normalise the rows exactly as its dgp_sync_*
+// does (dgp_rows.h), compare the engine against the image.
 int dgp_audit_tasks(dgp_engine* e, int64_t n, const int32_t* task, const uint8_t* state, const int32_t* remaining,
                     const int32_t* waiters, const int32_t* processing_on, const int64_t* nbytes,
                     const uint8_t* long_running, const uint8_t* wanted, const int64_t* holder_ptr,
                     const int32_t* holder_idx, int64_t cap, dgp_violation* out, int64_t* n_violations) {
   if (int rc_ = resident_stop(e)) return rc_;
-  if (int rc = row_audit_ready(e, "dgp_audit_tasks", cap, out, n_violations)) return rc;
-  if (n < 0 || (n > 0 && (!task || !state || !remaining || !waiters || !processing_on || !nbytes || !long_running ||
-                          !wanted || !holder_ptr)))
-    return fail(e, DGP_E_ARG, "dgp_audit_tasks: bad rows");
-  if (n == 0) return 0;
-  const dgp::Dev& D = e->D;
-  const int64_t H = holder_ptr[n];
-  if (holder_ptr[0] != 0 || H < 0 || (H > 0 && !holder_idx)) return fail(e, DGP_E_ARG, "dgp_audit_tasks: holder_ptr");
-  const size_t WB = (size_t)D.WB;
-  // what k_sync_tasks would write, per column; the columns a kernel reads only in some states
-  // are compared for the rows in those states (include/dgplace.h)
-  std::vector<int32_t> t_all(n), po(n), t_act, rem_act, t_mem, t_ho, ho, t_multi;
-  std::vector<uint8_t> st(n), lr(n), tf(n), multi;
-  std::vector<int64_t> cur_mem;
-  std::vector<uint64_t> rows((size_t)n * WB, 0);
-  for (int64_t i = 0; i < n; i++) {
-    const int32_t t = task[i];
-    if (t < 0 || t >= D.N || state[i] > dgp::S_ERRED + 1 || holder_ptr[i + 1] < holder_ptr[i])
-      return fail(e, DGP_E_ARG, "dgp_audit_tasks: task / state / holder_ptr");
-    if (state[i] == dgp::S_PROCESSING && (processing_on[i] < 0 || processing_on[i] >= D.W))
-      return fail(e, DGP_E_ARG, "dgp_audit_tasks: processing task without a worker");
-    int first = -1;
-    for (int64_t k = holder_ptr[i]; k < holder_ptr[i + 1]; k++) {
-      const int w = holder_idx[k];
-      if (w < 0 || w >= D.W) return fail(e, DGP_E_ARG, "dgp_audit_tasks: holder out of range");
-      rows[(size_t)i * WB + (w >> 6)] |= 1ull << (w & 63);
-      if (first < 0) first = w;
-    }
-    const bool forgotten = state[i] == dgp::S_ERRED + 1;
-    const uint8_t s = forgotten ? (uint8_t)dgp::S_RELEASED : state[i];
-    const int64_t hn = holder_ptr[i + 1] - holder_ptr[i];
-    t_all[i] = t;
-    st[i] = s;
-    po[i] = s == dgp::S_PROCESSING ? processing_on[i] : -1;
-    lr[i] = long_running[i] ? dgp::TD_LR : 0;
-    tf[i] = (uint8_t)((wanted[i] ? dgp::TF_WANTED : 0) | (forgotten ? dgp::TF_FORGOTTEN : 0));
-    if (s == dgp::S_WAITING || s == dgp::S_PROCESSING || s == dgp::S_QUEUED || s == dgp::S_NO_WORKER) {
-      t_act.push_back(t);
-      rem_act.push_back(remaining[i]);
-    }
-    if (s == dgp::S_MEMORY) {
-      t_mem.push_back(t);
-      cur_mem.push_back(nbytes[i] >= 0 ? nbytes[i] : D.default_data_size);
-    }
-    if (s == dgp::S_PROCESSING || (s == dgp::S_MEMORY && hn == 1)) {
-      t_ho.push_back(t);
-      ho.push_back(s == dgp::S_PROCESSING ? processing_on[i] : first);
-    }
-    if (hn > 1) {
-      t_multi.push_back(t);
-      multi.push_back(dgp::TD_MULTI);
-    }
-  }
+  if (int rc = audit_ready(e, "dgp_audit_tasks", false, cap, out, n_violations)) return rc;
+  rows::TaskImage img;
+  if (const char* bad = rows::task_rows(row_shape(e), n, task, state, remaining, waiters, processing_on, nbytes,
+                                        long_running, wanted, holder_ptr, holder_idx, img))
+    return fail(e, DGP_E_ARG, std::string("dgp_audit_tasks: ") + bad);
+  if (img.rows.empty()) return 0;
+  // the image, the holder list and scratch for the rows' who_has words: k_au_row_tasks compares
   RowAudit R;
-  const int RT = DGP_AR_ROW_TASKS;
-  const size_t ia = R.put(t_all.data(), (size_t)n * 4);
-  R.cmp(D.state, st.data(), n, 1, RT, DGP_AF_STATE, ia);
-  R.cmp(D.waiters, waiters, n, 4, RT, DGP_AF_WAITERS, ia);
-  R.cmp(D.proc_on, po.data(), n, 4, RT, DGP_AF_PROC_ON, ia);
-  R.cmp(D.res_nbytes, nbytes, n, 8, RT, DGP_AF_RES_NBYTES, ia);
-  R.cmp(D.holders, rows.data(), n * (int64_t)WB, 8, RT, DGP_AF_WHO_HAS, ia, (int)WB, ~0ull, 0);  // sub = the word
-  R.cmp(D.tdyn, lr.data(), n, 1, RT, DGP_AF_LR, ia, 1, dgp::TD_LR);
-  R.cmp(D.tflags, tf.data(), n, 1, RT, DGP_AF_WANTED, ia, 1, dgp::TF_WANTED);
-  R.cmp(D.tflags, tf.data(), n, 1, RT, DGP_AF_FORGOTTEN, ia, 1, dgp::TF_FORGOTTEN);
-  if (!t_act.empty())
-    R.cmp(D.remaining, rem_act.data(), (long long)t_act.size(), 4, RT, DGP_AF_REMAINING, R.put(t_act.data(), t_act.size() * 4));
-  if (!t_mem.empty())
-    R.cmp(D.cur_nbytes, cur_mem.data(), (long long)t_mem.size(), 8, RT, DGP_AF_CUR_NBYTES, R.put(t_mem.data(), t_mem.size() * 4));
-  if (!t_ho.empty())
-    R.cmp(D.holder_of, ho.data(), (long long)t_ho.size(), 4, RT, DGP_AF_HOLDER_OF, R.put(t_ho.data(), t_ho.size() * 4));
-  if (!t_multi.empty())
-    R.cmp(D.tdyn, multi.data(), (long long)t_multi.size(), 1, RT, DGP_AF_MULTI, R.put(t_multi.data(), t_multi.size() * 4), 1,
-          dgp::TD_MULTI);
+  const size_t o_rows = R.put(img.rows.data(), img.rows.size() * sizeof(rows::TaskRow));
+  const size_t o_hold = R.put(holder_idx, (size_t)holder_ptr[n] * 4);
+  const size_t o_who = R.put(nullptr, (size_t)n * e->D.WB * 8);
+  R.jobs.push_back(RowAudit::Job{3, nullptr, o_rows, o_hold, o_who, n, 1, 8, DGP_AR_ROW_TASKS, -1, -1, ~0ull, nullptr});
   return row_audit_run(e, R, cap, out, n_violations);
 }
 
@@ -3306,80 +3159,40 @@ int dgp_audit_workers(dgp_engine* e, int32_t n_workers, const int8_t* status, co
                       const int64_t* needs_ptr, const int32_t* needs_task, const int32_t* needs_count, int64_t cap,
                       dgp_violation* out, int64_t* n_violations) {
   if (int rc_ = resident_stop(e)) return rc_;
-  if (int rc = row_audit_ready(e, "dgp_audit_workers", cap, out, n_violations)) return rc;
+  if (int rc = audit_ready(e, "dgp_audit_workers", false, cap, out, n_violations)) return rc;
+  rows::WorkerImage img;
+  if (const char* bad = rows::worker_rows(row_shape(e), n_workers, status, nproc, n_long_running, plen, prefix, count,
+                                          netocc, nbytes, idle, saturated, needs_ptr, needs_task, needs_count, img))
+    return fail(e, DGP_E_ARG, std::string("dgp_audit_workers: ") + bad);
   const dgp::Dev& D = e->D;
-  namespace S = dgp::st;
   const int W = D.W;
-  if (n_workers != W || !status || !nproc || !n_long_running || !plen || !prefix || !count || !netocc || !nbytes ||
-      !idle || !saturated || !needs_ptr)
-    return fail(e, DGP_E_ARG, "dgp_audit_workers: one row per engine worker");
-  // dgp_sync_workers' normalisation, into what it would write
-  std::vector<int32_t> cap_(W), pf((size_t)W * dgp::PMAX, 0), pc((size_t)W * dgp::PMAX, 0), pl(W);
-  std::vector<uint8_t> fl(W);
-  std::vector<int64_t> slots(W, 0), nptr(W + 1, 0);
-  std::vector<uint32_t> ent;
-  int64_t tot[4] = {0, 0, 0, 0};  // idle, saturated, idle_task_count, its slots
   RowAudit R;
   const int RW = DGP_AR_ROW_WORKERS;
-  for (int w = 0; w < W; w++) {
-    if (status[w] < 0 || status[w] > 2) return fail(e, DGP_E_ARG, "dgp_audit_workers: status");
-    if (plen[w] < 0 || plen[w] > S::PD) return fail(e, DGP_E_ARG, "dgp_audit_workers: more than 8 prefixes on a worker");
-    const bool running = status[w] == 0;
-    if (!running && (idle[w] || saturated[w]))
-      return fail(e, DGP_E_ARG, "dgp_audit_workers: a worker that is not running is neither idle nor saturated");
-    if (status[w] != 2 && e->paused_h[w] == 2) return fail(e, DGP_E_ARG, "dgp_audit_workers: a removed worker returns");
-    if ((uint8_t)status[w] != e->paused_h[w])  // the host's copy of the status
-      R.host.push_back(dgp_violation{RW, DGP_AF_STATE, w, -1, e->paused_h[w], status[w]});
-    const int32_t nt = std::max<int32_t>(e->nthreads[w], 1);
-    const int32_t base = D.sat_inf ? 0 : std::max((int32_t)std::ceil(D.saturation * nt), (int32_t)1);
-    cap_[w] = base + (D.sat_inf ? 0 : n_long_running[w]);
-    pl[w] = plen[w];
-    for (int i = 0; i < plen[w]; i++) {
-      if (prefix[(size_t)w * S::PD + i] < 0 || prefix[(size_t)w * S::PD + i] >= D.P)
-        return fail(e, DGP_E_ARG, "dgp_audit_workers: prefix id");
-      pf[(size_t)w * dgp::PMAX + i] = prefix[(size_t)w * S::PD + i];
-      pc[(size_t)w * dgp::PMAX + i] = count[(size_t)w * S::PD + i];
-    }
-    const bool itc = running && (D.sat_inf || cap_[w] - nproc[w] > 0);
-    fl[w] = (uint8_t)((idle[w] ? dgp::WF_IDLE : 0) | (saturated[w] ? dgp::WF_SAT : 0) | (itc ? dgp::WF_ITC : 0) |
-                      (running ? 0 : dgp::WF_PAUSED));
-    slots[w] = itc && !D.sat_inf ? cap_[w] - nproc[w] : 0;
-    tot[0] += idle[w] ? 1 : 0;
-    tot[1] += saturated[w] ? 1 : 0;
-    tot[2] += itc ? 1 : 0;
-    tot[3] += slots[w];
-    const int64_t k0 = needs_ptr[w], k1 = needs_ptr[w + 1], m = k1 - k0;
-    if (k1 < k0 || (m > 0 && (!needs_task || !needs_count))) return fail(e, DGP_E_ARG, "dgp_audit_workers: needs_ptr");
-    if (m > (S::NLW - 1) + S::NXW) {  // scan mode: the entries are not compared; the kernel skips on the length
-      nptr[w + 1] = nptr[w] + m;
-      ent.resize(ent.size() + (size_t)m, 0u);
-      continue;
-    }
-    for (int64_t k = 0; k < m; k++) {
-      const int32_t d = needs_task[k0 + k], c = needs_count[k0 + k];
-      if (d < 0 || d >= D.N || c <= 0 || c > 255) return fail(e, DGP_E_ARG, "dgp_audit_workers: needs_what entry");
-      ent.push_back(((uint32_t)d << 8) | (uint32_t)c);
-    }
-    nptr[w + 1] = nptr[w] + m;
-  }
-  if (!D.sat_inf) R.cmp(D.w_cap, cap_.data(), W, 4, RW, DGP_AF_CAP);
+  for (int w = 0; w < W; w++)
+    if (img.status[w] != e->paused_h[w])  // the host's copy of the status
+      R.host.push_back(dgp_violation{RW, DGP_AF_STATE, w, -1, e->paused_h[w], img.status[w]});
+  if (!D.sat_inf) R.cmp(D.w_cap, img.cap.data(), W, 4, RW, DGP_AF_CAP);
   R.cmp(D.w_nproc, nproc, W, 4, RW, DGP_AF_NPROC);
-  R.cmp(D.w_plen, pl.data(), W, 4, RW, DGP_AF_DICT_LEN);
-  const size_t lim = R.put(pl.data(), (size_t)W * 4);
-  R.cmp(D.w_pfx, pf.data(), (long long)W * dgp::PMAX, 4, RW, DGP_AF_DICT_PREFIX, RowAudit::NONE, dgp::PMAX, ~0ull, -1, D.w_plen, lim);
-  R.cmp(D.w_pcnt, pc.data(), (long long)W * dgp::PMAX, 4, RW, DGP_AF_DICT_COUNT, RowAudit::NONE, dgp::PMAX, ~0ull, -1, D.w_plen, lim);
+  R.cmp(D.w_plen, img.plen.data(), W, 4, RW, DGP_AF_DICT_LEN);
+  const size_t lim = R.put(img.plen.data(), (size_t)W * 4);
+  R.cmp(D.w_pfx, img.pfx.data(), (long long)W * dgp::PMAX, 4, RW, DGP_AF_DICT_PREFIX, RowAudit::NONE, dgp::PMAX, ~0ull, -1,
+        D.w_plen, lim);
+  R.cmp(D.w_pcnt, img.pcnt.data(), (long long)W * dgp::PMAX, 4, RW, DGP_AF_DICT_COUNT, RowAudit::NONE, dgp::PMAX, ~0ull, -1,
+        D.w_plen, lim);
   R.cmp(D.w_netocc, netocc, W, 8, RW, DGP_AF_NETOCC);
   R.cmp(D.w_nbytes, nbytes, W, 8, RW, DGP_AF_NBYTES);
-  R.cmp(D.w_flags, fl.data(), W, 1, RW, DGP_AF_FLAGS);
-  if (!D.sat_inf) R.cmp(D.w_itcslots, slots.data(), W, 8, RW, DGP_AF_ITCSLOTS);
+  R.cmp(D.w_flags, img.flags.data(), W, 1, RW, DGP_AF_FLAGS);
+  if (!D.sat_inf) R.cmp(D.w_itcslots, img.slots.data(), W, 8, RW, DGP_AF_ITCSLOTS);
   const char* c = (const char*)e->ctl;
-  R.cmp(c + offsetof(dgp::Ctl, n_idle), &tot[0], 1, 8, RW, DGP_AF_N_IDLE);
-  R.cmp(c + offsetof(dgp::Ctl, n_sat), &tot[1], 1, 8, RW, DGP_AF_N_SAT);
-  R.cmp(c + offsetof(dgp::Ctl, n_itc), &tot[2], 1, 8, RW, DGP_AF_N_ITC);
-  if (!D.sat_inf) R.cmp(c + offsetof(dgp::Ctl, itc_slots), &tot[3], 1, 8, RW, DGP_AF_ITC_SLOTS);
-  if (ent.empty()) ent.push_back(0u);
-  R.jobs.push_back(RowAudit::Job{2, nullptr, R.put(nptr.data(), nptr.size() * 8), R.put(ent.data(), ent.size() * 4),
-                                 RowAudit::NONE, W, 1, 4, RW, DGP_AF_NEEDS_COUNT, -1, ~0ull, nullptr});
+  R.cmp(c + offsetof(dgp::Ctl, n_idle), &img.tot[0], 1, 8, RW, DGP_AF_N_IDLE);
+  R.cmp(c + offsetof(dgp::Ctl, n_sat), &img.tot[1], 1, 8, RW, DGP_AF_N_SAT);
+  R.cmp(c + offsetof(dgp::Ctl, n_itc), &img.tot[2], 1, 8, RW, DGP_AF_N_ITC);
+  if (!D.sat_inf) R.cmp(c + offsetof(dgp::Ctl, itc_slots), &img.tot[3], 1, 8, RW, DGP_AF_ITC_SLOTS);
+  // needs_what: the image's CSR as it is (k_au_row_needs skips a scan-mode row on its length)
+  if (img.needs.empty()) img.needs.push_back(0u);
+  R.jobs.push_back(RowAudit::Job{2, nullptr, R.put(img.needs_ptr.data(), img.needs_ptr.size() * 8),
+                                 R.put(img.needs.data(), img.needs.size() * 4), RowAudit::NONE, W, 1, 4, RW,
+                                 DGP_AF_NEEDS_COUNT, -1, ~0ull, nullptr});
   return row_audit_run(e, R, cap, out, n_violations);
 }
 
@@ -3389,18 +3202,12 @@ int dgp_audit_globals(dgp_engine* e, int64_t n_tasks_counter, double network_occ
                       const int64_t* group_released_waiting, const int64_t* group_left,
                       const int32_t* group_last_worker, int64_t cap, dgp_violation* out, int64_t* n_violations) {
   if (int rc_ = resident_stop(e)) return rc_;
-  if (int rc = row_audit_ready(e, "dgp_audit_globals", cap, out, n_violations)) return rc;
+  if (int rc = audit_ready(e, "dgp_audit_globals", false, cap, out, n_violations)) return rc;
+  if (const char* bad = rows::global_rows(row_shape(e), g_plen, g_prefix, g_count, n_queued, queued, duration_average,
+                                          max_exec_time, bandwidth, group_released_waiting, group_left,
+                                          group_last_worker))
+    return fail(e, DGP_E_ARG, std::string("dgp_audit_globals: ") + bad);
   const dgp::Dev& D = e->D;
-  if (g_plen < 0 || g_plen > dgp::PMAX_G || (g_plen > 0 && (!g_prefix || !g_count)) || n_queued < 0 ||
-      n_queued > D.N || (n_queued > 0 && !queued) || !duration_average || !max_exec_time || !(bandwidth > 0) ||
-      !group_released_waiting || !group_left || !group_last_worker)
-    return fail(e, DGP_E_ARG, "dgp_audit_globals: bad arguments");
-  for (int i = 0; i < g_plen; i++)
-    if (g_prefix[i] < 0 || g_prefix[i] >= D.P) return fail(e, DGP_E_ARG, "dgp_audit_globals: prefix id");
-  for (int64_t i = 0; i < n_queued; i++)
-    if (queued[i] < 0 || queued[i] >= D.N) return fail(e, DGP_E_ARG, "dgp_audit_globals: queued task");
-  for (int g = 0; g < D.G; g++)
-    if (group_last_worker[g] < -1 || group_last_worker[g] >= D.W) return fail(e, DGP_E_ARG, "dgp_audit_globals: last worker");
   RowAudit R;
   const int RG = DGP_AR_ROW_GLOBALS;
   const char* c = (const char*)e->ctl;
@@ -3414,7 +3221,8 @@ int dgp_audit_globals(dgp_engine* e, int64_t n_tasks_counter, double network_occ
   R.jobs.push_back(RowAudit::Job{1, nullptr, R.put(n_queued ? queued : &none, (size_t)std::max<int64_t>(n_queued, 1) * 4),
                                  RowAudit::NONE, RowAudit::NONE, n_queued, 1, 4, RG, DGP_AF_QUEUE_ENTRY, -1, ~0ull, nullptr});
   int k = 0;
-  for (const double* p : {D.pdur_cur, D.pdur_walk, D.pdur_pre}) R.cmp(p, duration_average, D.P, 8, RG, DGP_AF_DURATION, RowAudit::NONE, 1, ~0ull, k++);
+  for (const double* p : {D.pdur_cur, D.pdur_walk, D.pdur_pre})
+    R.cmp(p, duration_average, D.P, 8, RG, DGP_AF_DURATION, RowAudit::NONE, 1, ~0ull, k++);
   R.cmp(D.pmaxexec, max_exec_time, D.P, 8, RG, DGP_AF_MAX_EXEC);
   R.cmp(D.g_relwait, group_released_waiting, D.G, 8, RG, DGP_AF_RELWAIT);
   R.cmp(D.g_left, group_left, D.G, 8, RG, DGP_AF_GROUP_LEFT);

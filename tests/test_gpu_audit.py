@@ -279,11 +279,32 @@ def test_clean_at_every_round_boundary_in_service_mode(name, resident):
         assert p.skipped == 0
 
 
+def device_caps(eng, n_workers):
+    """w_cap of every worker, read through ``audit_rows``: against worker rows that claim 1,000
+    long-running tasks each, every cap differs, and each ``cap`` record carries the engine's
+    value."""
+    z = np.zeros(n_workers, np.int32)
+    rows = dict(status=z, nproc=z, n_long_running=z + 1000, plen=z, prefix=np.zeros(n_workers * PD, np.int32),
+                count=np.zeros(n_workers * PD, np.int32), netocc=z, nbytes=z, idle=z, saturated=z,
+                needs_ptr=np.zeros(n_workers + 1, np.int64), needs_task=z[:0], needs_count=z[:0])
+    found = eng.audit_rows(workers=rows, cap=128 * n_workers)
+    assert found.total == len(found)
+    caps = {v.index: v.device_value for v in found if v.rule == "ROW_WORKERS" and v.field == "cap"}
+    return [caps[w] for w in range(n_workers)]
+
+
 @pytest.mark.parametrize("name", [smallest([f for f in svc_add_worker_files() if f.startswith("svcaddw_order_")]),
-                                  "svcaddw_w1000_sat1.1.npz"])
+                                  "svcaddw_order_sat1.1.npz", "svcaddw_w1000_sat1.1.npz"])
 def test_clean_at_every_round_boundary_with_workers_joining(name):
     """Workers joining (dgp_add_worker_at: every later worker's index moves up on the device)
-    and, with 1,000 workers, worker state outside LDS and who_has rows of several words."""
+    and, with 1,000 workers, worker state outside LDS and who_has rows of several words.
+    After the last join every worker's slot cap is the cap rule of its own threads,
+    max(ceil(saturation * nthreads), 1), computed here and not by the engine (audit_state's cap
+    rule compares against the engine's own formula). The smallest svcaddw_order stream runs
+    under worker-saturation inf, where the cap is 0, nothing decides by it and no audit compares
+    it, so the cap is checked on the family's sat 1.1 stream and on the 1,000 workers."""
+    import math
+
     from distributed_amd.engine import PlacementEngine
 
     path = os.path.join(GOLDEN, name)
@@ -301,6 +322,9 @@ def test_clean_at_every_round_boundary_with_workers_joining(name):
     for i, w in zip(*((z["res_msg"].tolist(), z["res_worker"].tolist()) if "res_msg" in z else ((), ()))):
         add_at.setdefault(i, []).append((0, w, 2))
     R = len(exp["round_nplaced"]) + 2
+    nthreads, joined = g["nthreads"].tolist(), 0
+    sat = float(cfg["saturation"])
+    assert math.isfinite(sat) == ("satinf" not in name)
     with PlacementEngine(0) as eng:
         eng.load(g, cfg, snapshots=R, results=False)
         eng.update_graph()
@@ -314,6 +338,10 @@ def test_clean_at_every_round_boundary_with_workers_joining(name):
                         eng.set_worker_status(p_, 1)
                     else:
                         eng.add_worker(nt, running=bool(r_), position=p_)
+                        nthreads.insert(len(nthreads) if p_ is None else p_, nt)
+                        joined += 1
+                        if joined == n_add and math.isfinite(sat):  # the last join
+                            assert device_caps(eng, len(nthreads)) == [max(math.ceil(sat * t), 1) for t in nthreads]
                     p.check("snapshot")  # right after the join
                 j = i + 1
                 while j < e and j not in add_at:
@@ -761,6 +789,106 @@ def test_audit_rows_reports_exactly_the_altered_field(dumped):
     lw = int(gl["group_last_worker"][1])
     lw2 = (lw + 2) % W_
     check("globals", [V(G, "group_lastw", 1, -1, lw, lw2)], group_last_worker=bump(gl["group_last_worker"], 1, lw2 - lw))
+
+
+# ------------------------------------- 4b. the resync and its dry run share one set of rules
+def with_holder(tk, i, w):
+    """Task rows with worker ``w`` appended to row i's holder list."""
+    hp = tk["holder_ptr"].copy()
+    hp[i + 1:] += 1
+    return dict(tk, holder_ptr=hp, holder_idx=np.insert(tk["holder_idx"], int(tk["holder_ptr"][i + 1]), w))
+
+
+def test_a_refused_resync_changes_nothing(dumped):
+    """A resync call that is refused at its last row leaves the engine as it was: the rows
+    before it, valid and different from the engine's state, are not applied in part.
+
+    Workers: worker 0 goes running -> paused (idle and saturated cleared) and the last row
+    carries nine prefixes. On the parent of this change dgp_sync_workers had moved the host's
+    status column for worker 0 before it refused, and ``audit_rows`` reports it (ROW_WORKERS
+    ``state``, row 0). Tasks: row 0's ``wanted`` is flipped and the last row names a holder out
+    of range. On the parent dgp_sync_tasks had put the flag into the host's copy of the task
+    flags, which the next dgp_sync_workers uploads; so the original worker rows are resynced
+    before the audit, and the parent then reports ROW_TASKS ``wanted`` for row 0."""
+    from distributed_amd import _lib
+
+    eng, d = dumped
+    tk, wk, gl = d["tasks"], d["workers"], d["globals"]
+    W_ = len(wk["status"])
+    assert wk["status"][0] == 0 and W_ > 1
+    status, idle, sat, plen = wk["status"].copy(), wk["idle"].copy(), wk["saturated"].copy(), wk["plen"].copy()
+    status[0], idle[0], sat[0], plen[-1] = 1, 0, 0, 9
+    with pytest.raises(_lib.DgpError, match="more than 8 prefixes"):
+        eng.sync_workers(dict(wk, status=status, idle=idle, saturated=sat, plen=plen))
+    assert eng.audit_rows(tk, wk, gl) == [] and eng.audit_state() == ([], 0)
+    wanted = tk["wanted"].copy()
+    wanted[0] = 1 - wanted[0]
+    with pytest.raises(_lib.DgpError, match="holder out of range"):
+        eng.sync_tasks(dict(with_holder(tk, len(tk["task"]) - 1, W_), wanted=wanted))
+    eng.sync_workers(wk)  # uploads the host's copy of the task flags
+    assert eng.audit_rows(tk, wk, gl) == [] and eng.audit_state() == ([], 0)
+
+
+def malformed(d, N):
+    """(row kind, what is wrong, rows) for every input the resync refuses, over dump ``d`` of an
+    engine with N tasks."""
+    tk, wk, gl = d["tasks"], d["workers"], d["globals"]
+    W_, P_ = len(wk["status"]), len(gl["duration_average"])
+    PDs = 8
+
+    def at(a, i, v):
+        a = np.array(a).copy()
+        a[i] = v
+        return a
+
+    proc = int(np.nonzero(tk["state"] == 2)[0][0])
+    yield "tasks", "task id out of range", dict(tk, task=at(tk["task"], 0, N))
+    yield "tasks", "state 8", dict(tk, state=at(tk["state"], 0, 8))
+    yield "tasks", "descending holder_ptr", dict(tk, holder_ptr=at(tk["holder_ptr"], 1, -1))
+    yield "tasks", "holder out of range", with_holder(tk, len(tk["task"]) - 1, W_)
+    yield "tasks", "processing without a worker", dict(tk, processing_on=at(tk["processing_on"], proc, -1))
+    run, paused, removed = (int(np.nonzero(wk["status"] == s)[0][0]) for s in (0, 1, 2))
+    dicted = int(np.nonzero(wk["plen"] >= 1)[0][0])
+    nl = np.diff(wk["needs_ptr"])
+    k = int(wk["needs_ptr"][int(np.nonzero((nl >= 1) & (nl <= 63))[0][0])])  # a table the resync reads entry by entry
+    yield "workers", "status 3", dict(wk, status=at(wk["status"], run, 3))
+    yield "workers", "plen 9", dict(wk, plen=at(wk["plen"], run, 9))
+    yield "workers", "prefix id = P", dict(wk, prefix=at(wk["prefix"], dicted * PDs, P_))
+    yield "workers", "idle on a paused worker", dict(wk, idle=at(wk["idle"], paused, 1))
+    yield "workers", "a removed worker returns", dict(wk, status=at(wk["status"], removed, 1))
+    yield "workers", "needs count 0", dict(wk, needs_count=at(wk["needs_count"], k, 0))
+    yield "workers", "needs count 256", dict(wk, needs_count=at(wk["needs_count"], k, 256))
+    yield "workers", "needs task = N", dict(wk, needs_task=at(wk["needs_task"], k, N))
+    yield "workers", "descending needs_ptr", dict(wk, needs_ptr=at(wk["needs_ptr"], 1, -1))
+    many = 64 + 1  # PMAX_G (csrc/dgp_device.h): the prefixes the global dict holds
+    yield "globals", "g_plen = PMAX_G + 1", dict(gl, g_prefix=np.zeros(many, np.int32), g_count=np.ones(many, np.int64))
+    yield "globals", "prefix id = P", dict(gl, g_prefix=at(gl["g_prefix"], 0, P_))
+    yield "globals", "queued task = N", dict(gl, queued=at(gl["queued"], 0, N))
+    yield "globals", "last worker = W", dict(gl, group_last_worker=at(gl["group_last_worker"], 0, W_))
+    yield "globals", "bandwidth 0", dict(gl, bandwidth=0.0)
+
+
+def test_the_dry_run_refuses_what_the_resync_refuses_in_the_same_words(dumped):
+    """Every malformed input: dgp_sync_* and dgp_audit_* both refuse it, with the same message
+    once the function's name is taken out, and neither has changed anything (``audit_rows`` of
+    the dump is clean after each)."""
+    from distributed_amd import _lib
+
+    eng, d = dumped
+    tk, wk, gl = d["tasks"], d["workers"], d["globals"]
+    N = len(eng.task_states())
+    seen = 0
+    for kind, what, rows in malformed(d, N):
+        with pytest.raises(_lib.DgpError) as synced:
+            getattr(eng, f"sync_{kind}")(rows)
+        with pytest.raises(_lib.DgpError) as audited:
+            eng.audit_rows(**{"globals_" if kind == "globals" else kind: rows})
+        said = str(synced.value)
+        assert f"dgp_sync_{kind} failed (-1): dgp_sync_{kind}: " in said, (what, said)
+        assert str(audited.value) == said.replace(f"dgp_sync_{kind}", f"dgp_audit_{kind}"), (what, said, str(audited.value))
+        assert eng.audit_rows(tk, wk, gl) == [], what
+        seen += 1
+    assert seen == 19 and eng.audit_state() == ([], 0)
 
 
 # ----------------------------------------------------------------------- 5. read-only
