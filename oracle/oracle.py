@@ -57,6 +57,8 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.orc_replay.argtypes = [C.POINTER(OrcGraph), C.POINTER(OrcResult)]
         _lib.orc_replay.restype = C.c_int
+        _lib.orc_replay_at.argtypes = [C.POINTER(OrcGraph), C.POINTER(OrcResult), C.c_void_p, C.c_void_p]
+        _lib.orc_replay_at.restype = C.c_int
     return _lib
 
 
@@ -69,8 +71,11 @@ def replay(g: dict, config: dict, *, snapshots: bool = True, max_rounds: int | N
     """Replay graph ``g`` (graph dict, ``distributed_amd/graphs.py``) under ``config``
     ({bandwidth, default_data_size, unknown_duration, saturation}) and return the
     placement records + per-round snapshots as numpy arrays. ``joins``: (before, nthreads)
-    arrays of workers joining before the given completion (0-based, replay order); the
-    snapshots are then as wide as the final worker count. ``second``: (graph dict, before)
+    or (before, nthreads, position) arrays of running workers joining before the given
+    completion (0-based, replay order), each at the next index or at ``position`` (its rank
+    among the addresses of that moment: every index at or above it moves up); placements and
+    snapshot rows carry the indices of their time, the snapshots are as wide as the final
+    worker count. ``second``: (graph dict, before)
     — a later, independent graph (engine-wide prefix / group ids, priorities after ``g``'s)
     submitted before the given completion; its tasks follow ``g``'s in the outputs."""
     n = int(g["n_tasks"])
@@ -112,10 +117,13 @@ def replay(g: dict, config: dict, *, snapshots: bool = True, max_rounds: int | N
         gs.next = C.cast(C.pointer(gs2), C.c_void_p)
         gs.next_before = int(before)
         n += len(h["prio"])
+    join_pos = join_placed = None
     if joins is not None:
         gs.n_joins = len(joins[0])
         gs.join_before = _ptr(arr(joins[0], np.int64))
         gs.join_nthreads = _ptr(arr(joins[1], np.int32))
+        if len(joins) > 2:
+            join_pos = _ptr(arr(joins[2], np.int32))
     if g.get("restr_flags") is not None:  # worker restrictions, resolved to indices (graphs.restrict)
         gs.restr_ptr = _ptr(arr(g["restr_ptr"], np.int64))
         gs.restr_idx = _ptr(arr(g["restr_idx"], np.int32))
@@ -130,6 +138,9 @@ def replay(g: dict, config: dict, *, snapshots: bool = True, max_rounds: int | N
                     pl_start=_ptr(out["pl_start"]), pl_wsnbytes=_ptr(out["pl_wsnbytes"]),
                     pl_route=_ptr(out["pl_route"]), max_rounds=R, snap_stride=w, round_nplaced=_ptr(out["round_nplaced"]),
                     final_state=_ptr(out["final_state"]))
+    if joins is not None:
+        out["join_placed"] = np.zeros(len(joins[0]), np.int64)  # the placements made before each join
+        join_placed = _ptr(out["join_placed"])
     if snapshots:
         snap = dict(round_occ=np.zeros((R, w)), round_wnbytes=np.zeros((R, w), np.int64),
                     round_nproc=np.zeros((R, w), np.int32), round_idle=np.zeros((R, w), np.uint8),
@@ -138,7 +149,7 @@ def replay(g: dict, config: dict, *, snapshots: bool = True, max_rounds: int | N
         out.update(snap)
         for k, v in snap.items():
             setattr(res, k, _ptr(v))
-    rc = lib().orc_replay(C.byref(gs), C.byref(res))
+    rc = lib().orc_replay_at(C.byref(gs), C.byref(res), join_pos, join_placed)
     if rc != 0:
         raise RuntimeError("oracle replay failed: " + res.error.decode())
     np_ = int(res.n_placements)

@@ -61,7 +61,8 @@ struct orc_graph {
   const uint8_t* restr_flags;
   // workers joining mid-replay (optional, n_joins = 0: none): join k happens before the
   // join_before[k]-th completion (0-based, completions counted in replay order), with
-  // join_nthreads[k] threads and the next worker index (Scheduler.add_worker :4308-4441)
+  // join_nthreads[k] threads and the next worker index (Scheduler.add_worker :4308-4441);
+  // orc_replay_at gives each joiner a position instead
   int64_t n_joins;
   const int64_t* join_before;
   const int32_t* join_nthreads;
@@ -243,6 +244,13 @@ struct Replay {
   bool sat_inf;
   // recommendations scratch: position of a key inside the active Recs, -1 if absent
   std::vector<int32_t> rec_pos;
+  // the restriction rows by the worker indices of now (a private copy: a join below the
+  // worker count renumbers them)
+  std::vector<int32_t> restr_idx;
+
+  // orc_replay_at's arguments (null: every joiner takes the next index / nothing reported)
+  const int32_t* join_pos = nullptr;
+  int64_t* join_placed = nullptr;
 
   Replay(const orc_graph& g_, orc_result& r_) : g(g_), r(r_), N(g_.n_tasks), W(g_.n_workers) {
     G.append(g, 0);
@@ -275,6 +283,7 @@ struct Replay {
     build_group_deps();
     rootish_groups();
     idle.init((int)(W + g.n_joins));  // room for the workers that join (index order = address order)
+    if (g.restr_flags) restr_idx.assign(g.restr_idx, g.restr_idx + g.restr_ptr[g.n_tasks]);
   }
   void build_dependents() {  // TaskState.dependents (:1220), over the whole graph
     std::vector<int64_t> deg(N + 1, 0);
@@ -348,16 +357,33 @@ struct Replay {
     transitions(std::move(rc));
   }
 
-  void add_worker(int32_t nthreads) {
+  // pos: the joiner's rank in the SortedDict of addresses (:3746, :4353). The reference holds
+  // WorkerState objects, so nothing it keeps changes when the ranks do; this restatement holds
+  // indices, and every one >= pos moves up: who_has, processing_on, the groups' last_worker
+  // (:2176-2193), the idle structure (rebuilt from the workers' flags) and the restriction rows
+  // (valid_workers :3043-3107 names the same workers as before). Each map is monotone, so
+  // ascending rows and index-order ties stay what the SortedDict order makes them.
+  void add_worker(int32_t nthreads, int32_t pos) {
     ORC_CHECK(n_unrunnable == 0, "worker join with no-worker tasks: not in the replay subset");
+    ORC_CHECK(pos >= 0 && pos <= W, "worker join at a position past the worker count");
     Worker x;
     x.nthreads = nthreads;
     if (!sat_inf) x.slot_cap = std::max((int32_t)std::ceil(g.saturation * nthreads), (int32_t)1);
-    ws.push_back(x);
+    ws.insert(ws.begin() + pos, std::move(x));
+    if (pos < W) {
+      for (auto& h : who_has)
+        for (int32_t& w : h) w += w >= pos;
+      for (int32_t& w : processing_on) w += w >= pos;
+      for (Group& gr : groups) gr.last_worker += gr.last_worker >= pos;
+      for (int32_t& w : restr_idx) w += w >= pos;
+      idle.init((int)idle.n);
+      for (int32_t w = 0; w <= W; w++)
+        if (ws[w].idle) idle.add(w, 1);
+    }
     W++;
     total_nthreads += nthreads;
     rootish_groups();
-    check_idle_saturated((int32_t)(W - 1));
+    check_idle_saturated(pos);
     queue_slots_maybe_opened();
   }
 
@@ -542,7 +568,7 @@ struct Replay {
     if (W == 0) return -1;
     if (restricted(t)) {  // valid_workers(ts) is not None (every worker runs here)
       route = R_NONROOTISH;
-      std::vector<int32_t> valid(g.restr_idx + g.restr_ptr[t], g.restr_idx + g.restr_ptr[t + 1]);
+      std::vector<int32_t> valid(restr_idx.begin() + g.restr_ptr[t], restr_idx.begin() + g.restr_ptr[t + 1]);
       return decide_worker(t, &valid);
     }
     if (G.dep_ptr[t + 1] > G.dep_ptr[t]) {
@@ -860,7 +886,11 @@ struct Replay {
       round++;
       if (cur == done) break;
       for (int64_t i = done; i < cur; i++) {  // completions in run_id order
-        while (k_join < g.n_joins && g.join_before[k_join] <= n_done) add_worker(g.join_nthreads[k_join++]);
+        while (k_join < g.n_joins && g.join_before[k_join] <= n_done) {
+          if (join_placed) join_placed[k_join] = r.n_placements;
+          add_worker(g.join_nthreads[k_join], join_pos ? join_pos[k_join] : (int32_t)W);
+          k_join++;
+        }
         if (g.next && !next_done && g.next_before <= n_done) {
           next_done = true;
           add_graph(*g.next);
@@ -882,12 +912,23 @@ struct Replay {
 
 }  // namespace
 
-extern "C" int orc_replay(const orc_graph* g, orc_result* r) {
+// orc_replay with a position per joiner. join_pos[k] (null: the next index) is the index
+// joiner k takes, its rank among the addresses of that moment (workers is a SortedDict by
+// address, :3746, :4353): every index >= join_pos[k] the scheduler holds moves up by one.
+// Placements and snapshot rows carry the indices of their time. join_placed[k] (may be
+// null) receives the number of placements made before join k.
+extern "C" int orc_replay_at(const orc_graph* g, orc_result* r, const int32_t* join_pos, int64_t* join_placed);
+
+extern "C" int orc_replay(const orc_graph* g, orc_result* r) { return orc_replay_at(g, r, nullptr, nullptr); }
+
+extern "C" int orc_replay_at(const orc_graph* g, orc_result* r, const int32_t* join_pos, int64_t* join_placed) {
   r->n_placements = 0;
   r->n_rounds = 0;
   r->error[0] = 0;
   try {
     Replay rp(*g, *r);
+    rp.join_pos = join_pos;
+    rp.join_placed = join_placed;
     auto t1 = std::chrono::steady_clock::now();
     rp.run();
     auto t2 = std::chrono::steady_clock::now();

@@ -212,7 +212,7 @@ def replay_service(g, cfg, seed, p_inject=0.35, p_steal=0.0):
     return rec, rounds, nplaced, states, msgs, round_ptr, steals
 
 
-def replay_add_workers(g, cfg, seed, n_add, max_nthreads=4, interleave=False, n_paused=0):
+def replay_add_workers(g, cfg, seed, n_add, max_nthreads=4, interleave=False, n_paused=0, near=None):
     """The replay protocol's completions as task-finished messages, with ``n_add`` workers
     joining at random points of the first half of the stream, exactly as
     ``Scheduler.add_worker`` (distributed/scheduler.py:4308-4441) changes the placement
@@ -228,7 +228,10 @@ def replay_add_workers(g, cfg, seed, n_add, max_nthreads=4, interleave=False, n_
     ``add_nthreads``, ``add_pos`` (its index at the join), ``add_running``; ``res_msg`` /
     ``res_worker`` (the resumes: message index, the worker's index then); messages, placements
     and snapshots carry the index of their time; snapshots are as wide as the final worker
-    count (0 for workers not yet added)."""
+    count (0 for workers not yet added). ``near`` (with ``interleave``) states the initial
+    worker each joiner's address follows instead of drawing it, so that a stream can aim at a
+    position (a bitset word boundary); -1 is an address before every known one (position 0).
+    The rng draws are the same either way."""
     from distributed.core import Status
     from distributed.scheduler import Scheduler, WorkerState
 
@@ -245,6 +248,9 @@ def replay_add_workers(g, cfg, seed, n_add, max_nthreads=4, interleave=False, n_
     add_at = sorted(int(x) for x in rng.choice(N // 2, n_add, replace=False))
     add_nt = [int(x) for x in rng.integers(1, max_nthreads + 1, n_add)]
     add_near = [int(x) for x in rng.integers(0, W0, n_add)]  # interleave: the address follows worker j's
+    if near is not None:
+        assert interleave and len(near) == n_add and all(-1 <= j < W0 for j in near), near
+        add_near = [int(j) for j in near]
     paused_k = set(int(x) for x in rng.choice(n_add, n_paused, replace=False)) if n_paused else set()
     added = {"msg": [], "nthreads": [], "pos": [], "running": [], "addr": []}
     resumes = {"msg": [], "worker": []}
@@ -362,6 +368,35 @@ def main_add_workers(only):
                                  dict(interleave=True, n_paused=3)),
         # a live cluster's values under a config of its own (graphs.widen, G.WIDE_CONFIG)
         "svcaddw_wide_sat1.1": (lambda: wide_dag(1500, 24, 906, 916), 1.1, 13, 12),
+        # narrow restriction rows (1-4 of 12 workers, none empty) and appended joins
+        "svcaddw_restr12_sat1.1": (lambda: G.graphs.restrict(G.graphs.random_dag(1200, 12, seed=31, n_inner_prefixes=3,
+                                                                                  random_durations=True,
+                                                                                  nthreads="random"),
+                                                              0.3, seed=31, max_valid=4, empty_frac=0.0), 1.1, 14, 6),
+        # joins among the known addresses of a restricted graph: the restriction rows' worker
+        # indices move with every insertion (tests/test_join_census.py states what each reaches)
+        "svcaddw_insrestr_sat1.1": (lambda: G.graphs.restrict(G.graphs.random_dag(1200, 12, seed=32, n_inner_prefixes=3,
+                                                                                   random_durations=True,
+                                                                                   nthreads="random"),
+                                                               0.3, seed=32, max_valid=4, empty_frac=0.0), 1.1, 34, 6,
+                                    dict(interleave=True, n_paused=2)),
+        # the same graph with every joiner running: the inserted workers take queued tasks and
+        # later hold results (the oracle restates no paused worker, this stream it can follow)
+        "svcaddw_insq_sat1.1": (lambda: G.graphs.restrict(G.graphs.random_dag(1200, 12, seed=32, n_inner_prefixes=3,
+                                                                               random_durations=True,
+                                                                               nthreads="random"),
+                                                           0.3, seed=32, max_valid=4, empty_frac=0.0), 1.1, 30, 6,
+                                dict(interleave=True, n_paused=0)),
+        "svcaddw_insrestr_satinf": (lambda: G.graphs.restrict(G.graphs.random_dag(1500, 24, seed=33), 0.3, seed=33,
+                                                               max_valid=8, empty_frac=0.0), float("inf"), 16, 8,
+                                    dict(interleave=True, n_paused=0)),
+        # 62 workers growing to 70, the who_has bitsets from one 64-bit word to two: the join
+        # that takes the count from 64 to 65 inserts at 6, then joins at 0 and twice at 64
+        "svcaddw_ins64_sat1.1": (lambda: G.graphs.restrict(G.graphs.random_dag(2500, 62, seed=41, n_inner_prefixes=3,
+                                                                                random_durations=True,
+                                                                                nthreads="random"),
+                                                            0.3, seed=41, max_valid=8, empty_frac=0.0), 1.1, 17, 8,
+                                 dict(interleave=True, n_paused=0, near=[10, 61, 5, -1, 60, 40, 61, 59])),
     }
     for name, (mk, sat, seed, n_add, *kw) in cases.items():
         if only and name not in only:

@@ -87,7 +87,7 @@ def test_extension_follows_workers_joining():
     """Scheduler.add_worker mid-stream: the plugin hook adds the worker to the engine, and
     the scheduler's queue refill takes the engine's decisions (validate=True agrees)."""
     names = ["svcaddw_c2var_sat1.1.npz", "svcaddw_c2mini_sat1.0.npz", "svcaddw_c2mini_satinf.npz",
-             "svcaddw_restr_sat1.1.npz", "svcaddw_p16_sat1.1.npz"]
+             "svcaddw_restr_sat1.1.npz", "svcaddw_p16_sat1.1.npz", "svcaddw_restr12_sat1.1.npz"]
     res = drive(names)
     assert [r["fixture"] for r in res] == names
     for r in res:
@@ -99,13 +99,20 @@ def test_extension_follows_workers_joining_in_address_order():
     """Workers join at addresses that sort among the known ones (SortedDict order, scheduler.py
     :3746 / :4353) and some join paused, resuming later: the extension inserts each at its
     place (dgp_add_worker_at, every later index moves up) and stays active; every decision
-    is the engine's and validate=True agrees."""
-    names = ["svcaddw_order_sat1.1.npz", "svcaddw_order_satinf.npz"]
+    is the engine's and validate=True agrees. The svcaddw_ins* graphs carry worker
+    restrictions, which the extension resolves to engine indices itself: a stale index map
+    after an insertion would show here."""
+    paused = ["svcaddw_order_sat1.1.npz", "svcaddw_order_satinf.npz", "svcaddw_insrestr_sat1.1.npz"]
+    names = paused + ["svcaddw_insq_sat1.1.npz", "svcaddw_insrestr_satinf.npz", "svcaddw_ins64_sat1.1.npz"]
     res = drive(names)
+    assert [r["fixture"] for r in res] == names
     for r in res:
         assert r["active"] and r["device_decisions"] == r["placements"], r
         assert r["workers_added"] == r["joins"] > 0 and r["workers_inserted"] > 0, r
-        assert r["workers_added_paused"] > 0 and r["resumes"] > 0, r
+        if r["fixture"] in paused:
+            assert r["workers_added_paused"] > 0 and r["resumes"] > 0, r
+        else:
+            assert r["workers_added_paused"] == 0 and r["resumes"] == 0, r
 
 
 def test_extension_follows_a_second_graph():

@@ -294,10 +294,13 @@ def device_caps(eng, n_workers):
 
 
 @pytest.mark.parametrize("name", [smallest([f for f in svc_add_worker_files() if f.startswith("svcaddw_order_")]),
-                                  "svcaddw_order_sat1.1.npz", "svcaddw_w1000_sat1.1.npz"])
+                                  "svcaddw_order_sat1.1.npz", "svcaddw_w1000_sat1.1.npz",
+                                  "svcaddw_insrestr_sat1.1.npz", "svcaddw_ins64_sat1.1.npz"])
 def test_clean_at_every_round_boundary_with_workers_joining(name):
     """Workers joining (dgp_add_worker_at: every later worker's index moves up on the device)
-    and, with 1,000 workers, worker state outside LDS and who_has rows of several words.
+    and, with 1,000 workers, worker state outside LDS and who_has rows of several words;
+    svcaddw_insrestr / svcaddw_ins64: insertions into a restricted graph, the second across
+    the 64-worker word of the who_has rows (tests/test_join_census.py).
     After the last join every worker's slot cap is the cap rule of its own threads,
     max(ceil(saturation * nthreads), 1), computed here and not by the engine (audit_state's cap
     rule compares against the engine's own formula). The smallest svcaddw_order stream runs

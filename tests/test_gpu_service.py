@@ -432,8 +432,12 @@ def test_service_with_workers_joining(name, per_message):
         out.update(eng.snapshots(R))
         out["final_state"] = eng.task_states()
     assert (np.array(status) == 0).all()
-    if cfg["saturation"] != "inf":
-        assert refill > 0  # the joins took queued tasks
+    # the joins and resumes took the queued tasks the reference's took (stim_nplaced: update_graph,
+    # then every join, resume and completion in stream order)
+    kinds = [k for i in range(len(msgs)) for k in [0] * len(add_at.get(i, ())) + [1]]
+    assert refill == int(exp["stim_nplaced"][1:][np.array(kinds) == 0].sum())
+    if cfg["saturation"] != "inf" and exp["round_nqueued"].any():  # (svcaddw_ins64 has no root-ish group: no queue)
+        assert refill > 0
     assert_same(out, exp, PL_KEYS + ROUND_KEYS)
     assert np.array_equal(out["final_state"], exp["final_state"])
 

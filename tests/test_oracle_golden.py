@@ -57,22 +57,24 @@ def test_scenario_occupancy_includes_communication():
 @pytest.mark.parametrize("name", svc_add_worker_files())
 def test_oracle_matches_reference_with_workers_joining(name):
     """Workers joining mid-replay (Scheduler.add_worker, distributed/scheduler.py:4308-4441;
-    tests/golden/gen_service.py add-workers): the oracle's restatement against the
-    reference's placements, snapshots (as wide as the final worker count) and task states."""
+    tests/golden/gen_service.py add-workers), appended or at an address that sorts among the
+    known ones: the oracle's restatement against the reference's placements, snapshots (as
+    wide as the final worker count) and task states."""
     path = os.path.join(GOLDEN, name)
     g, cfg, exp, meta = oracle.load_fixture(path)
     z = np.load(path, allow_pickle=False)
-    if "add_pos" in z.files and (not z["add_running"].all() or
-                                 (z["add_pos"] != len(g["nthreads"]) + np.arange(len(z["add_pos"]))).any()):
-        # svcaddw_order_*: joins among the known addresses and paused joins. The oracle's
-        # restatement appends workers and has no paused workers (check_idle_saturated's
-        # paused branch, :2980-2981); these fixtures pin the engine directly against the
-        # reference's own placements (tests/test_gpu_service.py, tests/ext_driver.py)
-        pytest.skip("insertion / paused joins: pinned against the reference on the GPU, not restated by the oracle")
+    if "add_running" in z.files and not z["add_running"].all():
+        # svcaddw_order_*, svcaddw_insrestr_sat1.1: some joiners are paused. The oracle's
+        # restatement has no paused workers (check_idle_saturated's paused branch,
+        # :2980-2981); these fixtures pin the engine directly against the reference's own
+        # placements (tests/test_gpu_service.py, tests/ext_driver.py)
+        pytest.skip("paused joiners: pinned against the reference on the GPU, not restated by the oracle")
+    W0 = len(g["nthreads"])
+    pos = z["add_pos"] if "add_pos" in z.files else W0 + np.arange(len(z["add_msg"]))  # joins among the known addresses
     z = {"add_msg": z["add_msg"], "add_nthreads": z["add_nthreads"], "msg_task": z["msg_task"],
          "msg_nbytes": z["msg_nbytes"]}
     assert np.array_equal(z["msg_task"], exp["pl_task"])  # messages = completions in replay order
-    out = oracle.replay(g, cfg, joins=(z["add_msg"], z["add_nthreads"]))
+    out = oracle.replay(g, cfg, joins=(z["add_msg"], z["add_nthreads"], pos))
     assert_same(out, exp, PL_KEYS + ROUND_KEYS)
 
 
