@@ -51,6 +51,8 @@ SIGNATURES = {
     "dgp_graph_stimulus_ordered": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P]),
     "dgp_reschedule": (C.c_int, [_P, C.c_int32, _P]),
     "dgp_release_tasks": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    "dgp_set_release_mode": (C.c_int, [_P, C.c_int]),
+    "dgp_last_release_path": (C.c_int, [_P]),
     "dgp_add_graph_deferred": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P]),
     "dgp_snapshot": (C.c_int, [_P]),
     "dgp_num_placements": (C.c_int64, [_P]),
@@ -103,7 +105,7 @@ SIGNATURES = {
 }
 
 ABI_VERSION = 22
-ABI_REVISION = 1  # entry points added to ABI 22 (include/dgplace.h DGP_ABI_REVISION)
+ABI_REVISION = 2  # entry points added to ABI 22 (include/dgplace.h DGP_ABI_REVISION)
 _libs: dict = {}
 
 

@@ -11,7 +11,7 @@ DEPS = [os.path.join(PKG, "csrc", "dgp_device.h"), os.path.join(PKG, "csrc", "dg
         os.path.join(PKG, "csrc", "dgp_steal.h"), os.path.join(PKG, "csrc", "dgp_service.h"),
         os.path.join(PKG, "csrc", "dgp_events.h"), os.path.join(PKG, "csrc", "dgp_svcmsg.h"),
         os.path.join(PKG, "csrc", "dgp_msgs.h"), os.path.join(PKG, "csrc", "dgp_audit.h"),
-        os.path.join(PKG, "csrc", "dgp_rows.h")]
+        os.path.join(PKG, "csrc", "dgp_rows.h"), os.path.join(PKG, "csrc", "dgp_release.h")]
 OUT = os.path.join(PKG, "libdgplace.so")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 # -ffp-contract=off: no fused multiply-add, so fp64 results round exactly like the

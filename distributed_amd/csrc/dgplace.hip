@@ -39,6 +39,7 @@
 #define DGP_WAITC 0
 #include "dgp_stream.h"
 #include "dgp_events.h"
+#include "dgp_release.h"
 #include "dgp_steal.h"
 #include "dgp_service.h"
 #include "dgp_audit.h"
@@ -125,6 +126,10 @@ struct dgp_engine {
   size_t d_msgbuf_cap = 0;
   char* d_audit = nullptr;                 // dgp_audit_state scratch arena (device): grows with N, W, P
   size_t d_audit_cap = 0;
+  char* d_rel = nullptr;                   // dgp_release_tasks' bulk-path scratch arena (device): grows with n, N, W
+  size_t d_rel_cap = 0;
+  int release_mode = 0;                    // dgp_set_release_mode: 0 auto, 1 serial, 2 bulk
+  int last_release_path = 0;               // the path the last dgp_release_tasks ran: 1 serial, 2 bulk
   // resident service mode (dgp_set_resident): the stream kernel stays launched between
   // dgp_tasks_finished calls and takes each batch from a mailbox in pinned host memory
   dgp::svc::Mbox* mb = nullptr;      // host address
@@ -723,6 +728,7 @@ void dgp_destroy(dgp_engine* e) {
   if (e->d_ev) (void)hipFree(e->d_ev);
   if (e->d_msgbuf) (void)hipFree(e->d_msgbuf);
   if (e->d_audit) (void)hipFree(e->d_audit);
+  if (e->d_rel) (void)hipFree(e->d_rel);
   if (e->steal.arena) (void)hipFree(e->steal.arena);
   (void)hipFree(e->ctl);
   (void)hipFree(e->d_aux);
@@ -2366,6 +2372,96 @@ int event_with_refill(dgp_engine* e, F&& launch, int64_t* n_new_placements) {
   return 0;
 }
 
+// dgp_release_tasks' bulk path (dgp_release.h) for the staged plan d_task[n]. The scratch is
+// sized from n, N and W and allocated before the first launch. *ran = false: the read-only
+// pre-pass found a plan outside what the bulk path proves; nothing but scratch was written
+// and the caller runs the serial kernel.
+int release_bulk(dgp_engine* e, int64_t n, const int32_t* d_task, bool* ran, int64_t* n_new_placements) {
+  namespace rb = dgp::rb;
+  *ran = false;
+  const dgp::Dev& D = e->D;
+  if (D.P > rb::RB_PMAX || n > INT32_MAX) return 0;
+  const int N = D.N, W = D.W, m = (int)n;
+  hipStream_t s = e->stream;
+  size_t tmp_sel = 0, tmp_sort = 0;
+  rb::RbKeep keep{nullptr, nullptr};
+  HIPCHK(e, hipcub::DeviceSelect::If(nullptr, tmp_sel, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, N, keep, s));
+  HIPCHK(e, hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_sort, (unsigned long long*)nullptr,
+                                              (unsigned long long*)nullptr, m, 0, 64, s));
+  const size_t tmp_bytes = std::max(tmp_sel, tmp_sort);
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t sz[] = {al((size_t)N * 4), al((size_t)N * 4), al((size_t)m * 8), al((size_t)m * 8), al((size_t)m * 8),
+                       al((size_t)m * 4), al((size_t)W * 4), al((size_t)W * 4), al(sizeof(rb::Info)), al(tmp_bytes)};
+  size_t need = 0;
+  for (size_t b : sz) need += b;
+  if (need > e->d_rel_cap) {
+    HIPCHK(e, hipStreamSynchronize(s));
+    if (e->d_rel) (void)hipFree(e->d_rel);
+    e->d_rel = nullptr;
+    e->d_rel_cap = 0;
+    HIPCHK(e, hipMalloc((void**)&e->d_rel, need));
+    e->d_rel_cap = need;
+  }
+  char* p[10];
+  {
+    size_t off = 0;
+    for (int i = 0; i < 10; i++) {
+      p[i] = e->d_rel + off;
+      off += sz[i];
+    }
+  }
+  rb::Scratch R{(int32_t*)p[0], (int32_t*)p[1], (unsigned long long*)p[2], (unsigned long long*)p[3], (int64_t*)p[4],
+                (int32_t*)p[5], (int32_t*)p[6], (int32_t*)p[7], (rb::Info*)p[8]};
+  void* d_tmp = p[9];
+  if (int rc = grow_logs(e, 0)) return rc;
+  if (int rc = sync_dev(e)) return rc;
+  const int gN = grid_for(std::max(N, W), rb::RB_T, 4096), gn = (m + rb::RB_T - 1) / rb::RB_T;
+  hipLaunchKernelGGL(rb::k_rb_init, dim3(gN), dim3(rb::RB_T), 0, s, e->d_dev, R);
+  hipLaunchKernelGGL(rb::k_rb_scatter, dim3(gn), dim3(rb::RB_T), 0, s, R, d_task, m);
+  hipLaunchKernelGGL(rb::k_rb_classify, dim3(gn), dim3(rb::RB_T), 0, s, e->d_dev, R, d_task, m);
+  HIPCHK(e, hipGetLastError());
+  rb::Info info;
+  HIPCHK(e, hipMemcpyAsync(&info, R.info, sizeof info, hipMemcpyDeviceToHost, s));
+  dgp::Ctl c0;
+  if (int rc = read_ctl(e, &c0)) return rc;  // synchronises the stream
+  if (info.fallback) return 0;
+  if (info.n_exit < 0 || info.n_exit > m || c0.qlen < 0 || c0.qlen > N)
+    return fail(e, DGP_E_STATE, "dgp_release_tasks: the pre-pass counts are out of range");
+  *ran = true;
+  hipError_t cub = hipSuccess;
+  const int rc = event_with_refill(e, [&] {
+    hipLaunchKernelGGL(rb::k_rb_discard, dim3(gn), dim3(rb::RB_T), 0, s, e->d_dev, R, d_task, m);
+    if (info.n_queued > 0) {
+      if (c0.qlen > 0) {
+        size_t tb = tmp_bytes;
+        cub = hipcub::DeviceSelect::If(d_tmp, tb, D.qarr + c0.qhead, R.qtmp, &R.info->n_keep, (int)c0.qlen,
+                                       rb::RbKeep{R.pos, D.state}, s);
+        if (cub != hipSuccess) return;
+      }
+      hipLaunchKernelGGL(rb::k_rb_queue_store, dim3(grid_for(c0.qlen, rb::RB_T, 4096)), dim3(rb::RB_T), 0, s, e->d_dev,
+                         R, c0.qhead, c0.qlen);
+    }
+    const int nx = info.n_exit;
+    if (nx > 0) {
+      size_t tb = tmp_bytes;
+      cub = hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, R.key, R.skey, nx, 0, 64, s);
+      if (cub != hipSuccess) return;
+      hipLaunchKernelGGL(rb::k_rb_segments, dim3((nx + rb::RB_T - 1) / rb::RB_T), dim3(rb::RB_T), 0, s, R, nx);
+      hipLaunchKernelGGL(rb::k_rb_exits, dim3(W), dim3(64), 0, s, e->d_dev, R, d_task);
+      hipLaunchKernelGGL(rb::k_rb_flags, dim3(W), dim3(64), 0, s, e->d_dev, R, nx);
+    }
+    if (nx > 0 || info.n_nw > 0) hipLaunchKernelGGL(rb::k_rb_globals, dim3(1), dim3(rb::RB_T), 0, s, e->d_dev, R, nx);
+    hipLaunchKernelGGL(rb::k_rb_clamp, dim3(grid_for(N, rb::RB_T, 4096)), dim3(rb::RB_T), 0, s, e->d_dev);
+    hipLaunchKernelGGL(rb::k_rb_finish, dim3(gn), dim3(rb::RB_T), 0, s, e->d_dev, d_task, m);
+    hipLaunchKernelGGL(rb::k_rb_refill, dim3(1), dim3(64), 0, s, e->d_dev, e->d_aux + 3);
+  }, n_new_placements);
+  if (cub != hipSuccess) {
+    (void)hipStreamSynchronize(s);
+    return fail(e, DGP_E_HIP, std::string("dgp_release_tasks (bulk): ") + hipGetErrorString(cub));
+  }
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2476,11 +2572,31 @@ int dgp_release_tasks(dgp_engine* e, int64_t n, const int32_t* task, const uint8
   HIPCHK(e, hipMemcpy(const_cast<uint8_t*>(D.tflags), e->tflags_h.data(), D.N, hipMemcpyHostToDevice));
   std::vector<char*> a;
   if (int rc = stage_args(e, {{task, (size_t)n * 4}}, a)) return rc;
+  // the bulk path (dgp_release.h) for a large plan, or when asked for; the task-erred refill
+  // (n == 0) and every plan its pre-pass turns away take the serial kernel
+  if (n > 0 && (e->release_mode == 2 || (e->release_mode == 0 && n >= DGP_RELEASE_BULK_MIN))) {
+    bool ran = false;
+    const int rc = release_bulk(e, n, (const int32_t*)a[0], &ran, n_new_placements);
+    if (rc || ran) {
+      if (ran) e->last_release_path = 2;
+      return rc;
+    }
+  }
+  e->last_release_path = 1;
   return event_with_refill(e, [&] {
     hipLaunchKernelGGL(dgp::ev::k_ev_release_tasks, dim3(1), dim3(64), 0, e->stream, e->d_dev, (const int32_t*)a[0],
                        (int)n, e->d_aux + 3);
   }, n_new_placements);
 }
+
+int dgp_set_release_mode(dgp_engine* e, int mode) {
+  if (!e) return DGP_E_ARG;
+  if (mode < 0 || mode > 2) return fail(e, DGP_E_ARG, "dgp_set_release_mode: 0 auto, 1 serial, 2 bulk");
+  e->release_mode = mode;
+  return 0;
+}
+
+int dgp_last_release_path(dgp_engine* e) { return e ? e->last_release_path : 0; }
 
 int dgp_heartbeat(dgp_engine* e, double bandwidth, int64_t n, const int32_t* prefix, const double* duration) {
   if (int rc_ = resident_stop(e)) return rc_;

@@ -552,7 +552,10 @@ class PlacementEngine:
         from its state -- a result with its replicas, cancelled work (processing, waiting,
         queued, no-worker) leaving its worker / the queue and its dependencies' waiters --
         forgotten where flagged, then the queue refill. Returns its placements, or None when the
-        engine leaves it to the scheduler (an erred or forgotten task), with nothing changed."""
+        engine leaves it to the scheduler (an erred or forgotten task), with nothing changed.
+        The device applies the plan on one lane (a few tasks) or, from DGP_RELEASE_BULK_MIN
+        tasks on, in parallel over tasks, queue and workers (a cancelled graph), with the same
+        result: ``set_release_mode`` picks, ``last_release_path`` tells which ran."""
         t, f = self._arr(task, np.int32), self._arr(forget, np.uint8)
         if len(t) != len(f):
             raise ValueError("one forget flag per task")
@@ -563,6 +566,19 @@ class PlacementEngine:
             return None
         self._check(rc, "dgp_release_tasks")
         return int(newp.value)
+
+    RELEASE_AUTO, RELEASE_SERIAL, RELEASE_BULK = 0, 1, 2
+
+    def set_release_mode(self, mode: int = 0):
+        """The device path of ``release_tasks`` (dgp_set_release_mode): 0 by the plan's size,
+        1 the serial kernel, 2 the bulk kernels (which still leave the plans they do not
+        cover to the serial one)."""
+        self._check(self.lib.dgp_set_release_mode(self.h, int(mode)), "dgp_set_release_mode")
+
+    @property
+    def last_release_path(self) -> int:
+        """The path the last ``release_tasks`` ran: 1 serial, 2 bulk, 0 before the first."""
+        return int(self.lib.dgp_last_release_path(self.h))
 
     @staticmethod
     def _order_rows(order):

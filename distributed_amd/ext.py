@@ -818,6 +818,8 @@ class GPUPlacementExtension(SchedulerPlugin):
                 self.fallback(f"{what}: {e}")
             return None
         self.stats[what] += 1
+        if what == "release_tasks" and getattr(self.engine, "last_release_path", 0) == 2:
+            self.stats["release_tasks_bulk"] += 1  # the plan ran on the bulk kernels
         self._fetch()  # a refill the operation made (resume, long-running)
         if self.validate and r is not None and what in ("release_tasks", "reschedule"):
             self._audit_validate(what)

@@ -72,8 +72,8 @@ extern "C" {
 
 #define DGP_ABI_VERSION 22
 /* Entry points added since, every ABI 22 signature unchanged (a caller built against ABI 22
- * runs as before): 1 = dgp_num_unrunnable. */
-#define DGP_ABI_REVISION 1
+ * runs as before): 1 = dgp_num_unrunnable; 2 = dgp_set_release_mode, dgp_last_release_path. */
+#define DGP_ABI_REVISION 2
 
 #define DGP_OK 0
 #define DGP_E_ARG -1     /* invalid argument / shape */
@@ -313,8 +313,25 @@ int dgp_graph_stimulus(dgp_engine* e, int64_t* n_new_placements);
  * dependents walk and out of its TaskGroup's states["released"], ABI 22). Each task is listed
  * once. Then the queue refill (:5430). *n_new_placements: its placements.
  * DGP_E_UNSUPPORTED with nothing changed for an erred or forgotten task (the scheduler
- * decides, then dgp_sync_*). */
+ * decides, then dgp_sync_*).
+ * Two device paths apply the plan and leave the same state. The serial one walks it on one
+ * lane (each queued task searched in the queue: n * len(queued) steps), the path for a few
+ * tasks. The bulk one (revision 2) is parallel over the tasks, the queue and the workers, the
+ * path for a cancelled graph: plans of DGP_RELEASE_BULK_MIN tasks and more take it unless
+ * dgp_set_release_mode says otherwise. A plan that lists a result's release before a
+ * cancelled dependent of it that is processing on a worker whose needs_what is in scan mode
+ * takes the serial path whatever the mode, as does n == 0. */
 int dgp_release_tasks(dgp_engine* e, int64_t n, const int32_t* task, const uint8_t* forget, int64_t* n_new_placements);
+/* the smallest plan the automatic mode gives to the bulk path: the smallest measured size
+ * from which it is not slower than the serial path with and without queued tasks, as a power
+ * of two (profiles/bulk_release/crossover.txt) */
+#define DGP_RELEASE_BULK_MIN 64
+/* dgp_set_release_mode (revision 2): the path dgp_release_tasks takes: 0 by the plan's size
+ * (the default), 1 serial, 2 bulk (still serial for the plans named above). */
+int dgp_set_release_mode(dgp_engine* e, int mode);
+/* dgp_last_release_path (revision 2): the path the last dgp_release_tasks ran: 1 serial,
+ * 2 bulk, 0 before the first call. */
+int dgp_last_release_path(dgp_engine* e);
 /* dgp_reschedule (ABI 21): Scheduler._reschedule (scheduler.py:7900-7924) of a processing task
  * -- transitions({key: "released"}): it leaves its worker (check_idle_saturated), is
  * recommended waiting when something needs it and placed again by decide_worker, through the
