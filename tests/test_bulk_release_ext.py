@@ -19,7 +19,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 PY39 = "/opt/conda/bin/python3.9"
 HAVE_REF = os.path.exists(PY39) and os.path.isdir("/root/reference/distributed")
-STREAMS = ["bulk/svcbulk_all_c2var_sat1.1.npz", "bulk/svcbulk_queue_sat1.1.npz"]  # under tests/golden/
+STREAMS = ["bulk/svcbulk_all_c2var_sat1.1.npz", "bulk/svcbulk_queue_sat1.1.npz",
+           "bulk/svcbulk_skew_satinf.npz"]  # under tests/golden/
 BULK_MIN = 64  # include/dgplace.h DGP_RELEASE_BULK_MIN
 
 
