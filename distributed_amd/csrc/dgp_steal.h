@@ -318,8 +318,10 @@ __global__ void k_thief_keys(Prob P) {
   const int w = blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= P.W) return;
   const bool th = P.idle[w] != 0;
-  const double a = P.occ[w] / (double)P.nthreads[w];
-  P.tk_a[w] = th ? (uint64_t)__double_as_longlong(a) : ~0ull;  // a >= 0: bits order like values
+  // a >= 0 (dgp_steal_load refuses a negative or NaN occupancy), so the bits order like the
+  // values; + 0.0 (exact) turns the one exception, -0.0, into +0.0: the same run as 0.0
+  const double a = P.occ[w] / (double)P.nthreads[w] + 0.0;
+  P.tk_a[w] = th ? (uint64_t)__double_as_longlong(a) : ~0ull;
   P.tk_nb[w] = P.wnbytes[w];
   P.tk_w[w] = w;
 }
@@ -363,6 +365,9 @@ __device__ __forceinline__ int64_t rl_i64s(int64_t x, int l) {  // lane l's int6
   const unsigned lo = __builtin_amdgcn_readlane((unsigned)x, l), hi = __builtin_amdgcn_readlane((unsigned)(x >> 32), l);
   return (int64_t)(((uint64_t)hi << 32) | lo);
 }
+// 37 W + 4 bytes: with 160 KiB of LDS that admits 4,428 workers. The layout is restated by hand
+// in tests/test_gpu_steal_edges.py (_lds_bytes) and the limit in include/dgplace.h
+// (dgp_steal_balance): change them with it.
 __host__ __device__ inline size_t balance_state_bytes(int W) {
   return (size_t)W * (8 + 8 + 4) + ((size_t)6 * W + 2) * 2 + (size_t)W * 4 + (size_t)W;
 }

@@ -784,6 +784,9 @@ int dgp_conflict_depth(int64_t n_tasks, const int64_t* dep_ptr, const int32_t* d
  * computed by steal_time_ratio), inflight_*_in = in_flight_occupancy / in_flight_tasks
  * of unconfirmed steals (null: none); the in-flight outputs are then the new totals, and
  * checked_out[w] = 1 for each victim check_idle_saturated ran on (:498-500).
+ * Limits (DGP_E_ARG): nthreads in 1..65535; n_workers at most 4,428 (the walk's per-worker
+ * state in 160 KiB of LDS: balance_state_bytes, csrc/dgp_steal.h, which names this line); occupancy not negative and not NaN (-0.0 counts as 0.0): the
+ * thieves are ordered by the bits of occupancy / nthreads.
  * Kernel-time ids 4 (levels + bins),
  * 5 (thief argmin), 6 (balance walk). */
 int dgp_steal_balance(dgp_engine* e, int32_t n_workers, const int32_t* nthreads, const double* occupancy,

@@ -253,7 +253,9 @@ def load_steal_fixture(path: str):
     p = {k: z[k] for k in STEAL_INPUTS}
     for k in ("total_occ", "total_nthreads", "bandwidth"):
         p[k] = z[k][()]
-    for k in ("holder_ptr", "holder_idx", "restr_ptr", "restr_idx", "restr_flags"):
+    for k in ("holder_ptr", "holder_idx", "restr_ptr", "restr_idx", "restr_flags",
+              # the plugin's state before a balance() that follows an unconfirmed one
+              "level_in", "inflight_occ_in", "inflight_tasks_in"):
         if k in z.files:
             p[k] = z[k]
     exp = {k: z[k] for k in ("level", "st_task", "st_level", "st_cost", "st_victim", "st_occ_victim", "st_thief",
