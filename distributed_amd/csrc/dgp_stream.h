@@ -95,6 +95,7 @@ __constant__ Dev c_dev;
 #ifndef DGP_SCTA
 #define DGP_SCTA 1024
 #endif
+#define DGP_COLD __attribute__((noinline, cold))
 constexpr int SCTA = DGP_SCTA;   // 1024: 16 waves = 5 roles + 11 executors (128 VGPRs per wave; 768/7 executors: C2 1.18 s, 1024: 1.14 s)
 #ifndef DGP_WIN
 #define DGP_WIN 32
@@ -677,6 +678,8 @@ __device__ __attribute__((always_inline)) void serr(SCtl& S, int code, int task)
   if (atomicCAS(&S.error, 0, code) == 0) S.err_task = task;
   vstore(&S.stop, 1);
 }
+// the executors' error exits, out of line (never on a taken path)
+__device__ DGP_COLD void serr_cold(int code, int task) { serr(st_L().c, code, task); }
 
 
 // The watchdog runs on s_memrealtime, the constant 100 MHz counter (s_memtime is the
@@ -2227,74 +2230,117 @@ __device__ __attribute__((always_inline)) int64_t needs_inc(const Dev& D, SCtl& 
   return nb;
 }
 
-// All of one task's dependency entries at once. A task's dependencies are distinct, so
-// their needs_what entries are distinct lanes of the line: each dependency is matched
-// against the line in one compare (no readlane chain through the line). Fast path only
-// when every entry of c lives in the LDS line (no overflow entries, not scan mode) and
-// the outcome needs no overflow entry; otherwise false with nl untouched, and the caller
-// takes the one-at-a-time path (needs_dec / needs_inc).
-// _dec_needs_replica (:815-823) for the dependencies in entries L0.. of E not held by c;
-// freed = the bytes c no longer needs.
 // lane masks of a comparison over the (active) lanes: one v_cmp into an SGPR pair
 __device__ __forceinline__ unsigned long long lm_eq(unsigned a, unsigned b) { return __builtin_amdgcn_uicmp(a, b, 32); }
 __device__ __forceinline__ unsigned long long lm_ne(unsigned a, unsigned b) { return __builtin_amdgcn_uicmp(a, b, 33); }
 __device__ __forceinline__ bool lm_has(unsigned long long m) { return (m >> lane_id()) & 1ull; }
 constexpr unsigned long long NL_LINE = (1ull << (NLW - 1)) - 1;  // the line's entry lanes
 
-__device__ __forceinline__ bool needs_dec_all(const uint4& E, int L0, int k, int c, uint32_t& nl, int64_t& freed) {
+// f(0) .. f(k - 1): the first four calls unrolled, so that an f that reads lane `base + i`
+// of a register with a constant base reads a constant lane (no lane-index arithmetic in
+// front of the v_readlane); the rest in a loop
+template <class F>
+__device__ __forceinline__ void each_dep(int k, F&& f) {
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+    if (i < k) f(i);
+  for (int i = 4; i < k; i++) f(i);
+}
+
+// All of one task's dependency entries at once. A task's dependencies are distinct, so
+// their needs_what entries are distinct lanes of the line: each dependency is matched
+// against the line in one compare (no readlane chain through the line). Fast path only
+// when every entry of c lives in the LDS line (no overflow entries, not scan mode) and
+// the outcome needs no overflow entry; otherwise false with nl untouched, and the caller
+// takes the one-at-a-time path (needs_dec / needs_inc). What sends a dependency to that path
+// is noted and tested once after the last one (no exit inside the unrolled run).
+// The line as both see it: ok = every entry of the worker is in the line.
+struct NeedsLine {
+  uint32_t key;             // this lane's entry: the dependency
+  unsigned long long used;  // lanes holding an entry
+  bool ok;
+};
+__device__ __forceinline__ NeedsLine needs_line(uint32_t nl) {
   const uint32_t ctl = rlu(nl, NLW - 1);
-  const unsigned long long used = lm_ne(nl, 0u) & NL_LINE;
-  if (ctl == NL_OVF || (int)(ctl >> 8) != __builtin_popcountll(used)) return false;
-  const uint32_t key = nl >> 8;
-  const unsigned long long one = lm_eq(nl & 0xffu, 1u) & used;  // entries this decrement empties
+  NeedsLine n;
+  n.used = lm_ne(nl, 0u) & NL_LINE;
+  n.ok = ctl != NL_OVF && (int)(ctl >> 8) == __builtin_popcountll(n.used);
+  n.key = nl >> 8;
+  return n;
+}
+
+// _dec_needs_replica (:815-823) for the dependencies in entries L0..L0+k-1 of E not held by c;
+// freed = the bytes c no longer needs. (The completing task's entries start at the constant
+// E_HDR: constant-lane reads for its first four.)
+__device__ __forceinline__ bool needs_dec_all(const uint4& E, int L0, int k, int c, uint32_t& nl, int64_t& freed) {
+  const NeedsLine n = needs_line(nl);
+  if (!n.ok) return false;
+  const unsigned long long one = lm_eq(nl & 0xffu, 1u) & n.used;  // entries this decrement empties
   unsigned long long hit = 0;
   int64_t fr = 0;
   int ngone = 0;
-  for (int i = 0; i < k; i++) {
-    if (rl((int)E.y, L0 + i) == c) continue;  // held by c: never needed
-    const unsigned long long m = lm_eq(key, rlu(E.x, L0 + i)) & used;
-    if (!m) return false;  // not in the line (overflow / replica events): the general path
+  bool miss = false;  // not in the line (overflow / replica events): the general path
+  each_dep(k, [&](int i) {
+    const int l = L0 + i;
+    if (rl((int)E.y, l) == c) return;  // held by c: never needed
+    const unsigned long long m = lm_eq(n.key, rlu(E.x, l)) & n.used;
+    miss = miss || !m;
     hit |= m;
     if (m & one) {
-      fr += mk64(rlu(E.z, L0 + i), rlu(E.w, L0 + i));
+      fr += mk64(rlu(E.z, l), rlu(E.w, l));
       ngone++;
     }
-  }
+  });
+  if (miss) return false;
   if (hit) nl = lm_has(hit & one) ? 0u : (lm_has(hit) ? nl - 1u : nl);
   if (ngone) nl = lane_id() == NLW - 1 ? nl - ((uint32_t)ngone << 8) : nl;
   freed = fr;
   return true;
 }
 
-// _inc_needs_replica (:800-813) for the dependencies in entries L0.. of E not held by c
-// (task placed on c); added = the bytes c newly needs.
+// the descriptor entries from entry `first` on, moved down to lanes 0..: a frontier task's
+// dependency entries start at a lane that differs from stimulus to stimulus; moved once, every
+// read of them below is a readlane at a constant lane. Call it with all 64 lanes active
+// (ds_bpermute returns 0 for a lane whose source lane is off): exe_local's control flow is
+// wave-uniform, every branch there is on a ballot or a readlane.
+__device__ __forceinline__ uint4 entries_from(const uint4& E, int first) {
+  const int a = ((lane_id() + first) & 63) << 2;
+  return make_uint4((unsigned)__builtin_amdgcn_ds_bpermute(a, (int)E.x), (unsigned)__builtin_amdgcn_ds_bpermute(a, (int)E.y),
+                    (unsigned)__builtin_amdgcn_ds_bpermute(a, (int)E.z), (unsigned)__builtin_amdgcn_ds_bpermute(a, (int)E.w));
+}
+
+// _inc_needs_replica (:800-813) for the dependencies in entries L0..L0+k-1 of E not held by c
+// (task placed on c); added = the bytes c newly needs. (exe_local passes a frontier task's
+// entries moved to lane 0, entries_from: constant-lane reads for its first four.)
 __device__ __forceinline__ bool needs_inc_all(const uint4& E, int L0, int k, int c, uint32_t& nl, int64_t& added) {
-  const uint32_t ctl = rlu(nl, NLW - 1);
-  const unsigned long long used = lm_ne(nl, 0u) & NL_LINE;
-  if (ctl == NL_OVF || (int)(ctl >> 8) != __builtin_popcountll(used)) return false;
-  const uint32_t key = nl >> 8;
-  const unsigned long long full = lm_eq(nl & 0xffu, 0xffu) & used;
-  unsigned long long freem = ~used & NL_LINE;
+  const NeedsLine n = needs_line(nl);
+  if (!n.ok) return false;
+  const unsigned long long full = lm_eq(nl & 0xffu, 0xffu) & n.used;
+  unsigned long long freem = ~n.used & NL_LINE;
   unsigned long long hit = 0;
   uint32_t nn = nl;
   int64_t ad = 0;
   int nins = 0;
-  for (int i = 0; i < k; i++) {
-    if (rl((int)E.y, L0 + i) == c) continue;
-    const uint32_t d = rlu(E.x, L0 + i);
-    const unsigned long long m = lm_eq(key, d) & used;  // against the line as loaded (deps are distinct)
+  bool bad = false;  // a full count, or no free entry in the line (overflow entries): the general path
+  each_dep(k, [&](int i) {
+    const int l = L0 + i;
+    if (rl((int)E.y, l) == c) return;
+    const uint32_t d = rlu(E.x, l);
+    const unsigned long long m = lm_eq(n.key, d) & n.used;  // against the line as loaded (deps are distinct)
     if (m) {
-      if (m & full) return false;
+      bad = bad || (m & full);
       hit |= m;
+    } else if (!freem) {
+      bad = true;
     } else {
-      if (!freem) return false;  // the line is full: the general path (overflow entries)
-      const int l = __builtin_ctzll(freem);
+      const int f = __builtin_ctzll(freem);
       freem &= freem - 1;
-      nn = lane_id() == l ? (d << 8) | 1u : nn;
-      ad += mk64(rlu(E.z, L0 + i), rlu(E.w, L0 + i));
+      nn = lane_id() == f ? (d << 8) | 1u : nn;
+      ad += mk64(rlu(E.z, l), rlu(E.w, l));
       nins++;
     }
-  }
+  });
+  if (bad) return false;
   if (hit) nn = lm_has(hit) ? nn + 1u : nn;
   if (nins) nn = lane_id() == NLW - 1 ? nn + ((uint32_t)nins << 8) : nn;
   nl = nn;
@@ -2481,6 +2527,13 @@ __device__ __forceinline__ uint64_t rl64(uint64_t v, int l) {
 
 // the resolved durations of a stimulus (descriptor entries 3..6, in lanes 3..6 of E) into
 // the executor wave's LDS table, read by prefix id (one wave's LDS operations run in order)
+// (more prefixes than the descriptor carries, out of line: the stimulus' duration row)
+__device__ DGP_COLD void dur_row_cold(long long r) {
+  const Dev& D = c_dev;
+  const int lane = lane_id();
+  const auto t = (__attribute__((address_space(3))) double*)(double*)st_L().dur[threadIdx.x >> 6];
+  if (lane < D.P) t[lane] = D.dring[(size_t)(r & (DR - 1)) * PX + lane];
+}
 __device__ __forceinline__ DTab stim_durations(const Dev& D, SLds& L, const uint4& E, long long r) {
   const int lane = lane_id();
   const auto t = (__attribute__((address_space(3))) double*)(double*)L.dur[threadIdx.x >> 6];
@@ -2489,11 +2542,74 @@ __device__ __forceinline__ DTab stim_durations(const Dev& D, SLds& L, const uint
       t[2 * (lane - 3)] = mkd(E.x, E.y);
       t[2 * (lane - 3) + 1] = mkd(E.z, E.w);
     }
-  } else if (lane < D.P) {  // more prefixes than the descriptor carries: the stimulus' row
-    t[lane] = D.dring[(size_t)(r & (DR - 1)) * PX + lane];
+  } else {  // more prefixes than the descriptor carries: the stimulus' row
+    dur_row_cold(r);
   }
   return (DTab)(const double*)t;
 }
+
+// ---- exe_local's fallbacks, out of line: the taken path (a local stimulus that is not exact,
+// the whole-line needs updates succeeding, unrestricted frontier tasks, one thread per touched
+// worker, P <= PD) stays one run of blocks in the executor's loop, and what only a fallback
+// needs is live only inside it. Values go in and come back in registers (no references: a
+// reference to a caller's local would put it in scratch).
+struct NeedsRes {
+  uint32_t nl;  // this lane's word of the worker's needs line, updated
+  int64_t v;    // bytes freed / newly needed (uniform)
+};
+// _dec_needs_replica one dependency at a time (overflow entries, scan mode, replica events):
+// entries L0..L0+k-1 of E, task t leaving worker c
+__device__ DGP_COLD NeedsRes needs_dec_each(uint4 E, int L0, int k, int c, uint32_t nl, int t) {
+  const Dev& D = c_dev;
+  SCtl& S = st_L().c;
+  int64_t v = 0;
+  for (int i = 0; i < k; i++) {
+    const int L_ = L0 + i;
+    if (rl((int)E.y, L_) == c) continue;
+    v += needs_dec(D, S, c, nl, rl((int)E.x, L_), mk64(rlu(E.z, L_), rlu(E.w, L_)), t);
+  }
+  return NeedsRes{nl, v};
+}
+// _inc_needs_replica one dependency at a time: task x placed on worker c
+__device__ DGP_COLD NeedsRes needs_inc_each(uint4 E, int L0, int k, int c, uint32_t nl, int x) {
+  const Dev& D = c_dev;
+  SCtl& S = st_L().c;
+  int64_t v = 0;
+  for (int i = 0; i < k; i++) {
+    const int L2 = L0 + i;
+    if (rl((int)E.y, L2) == c) continue;
+    v += needs_inc(D, S, c, nl, rl((int)E.x, L2), mk64(rlu(E.z, L2), rlu(E.w, L2)), x);
+  }
+  return NeedsRes{nl, v};
+}
+// a restricted task's resolved candidates (entries L0..L0+nc-1): is this lane's worker one
+__device__ DGP_COLD bool restr_cand_cold(unsigned ex, int L0, int nc, int cj) {
+  bool cand = false;
+  for (int i = 0; i < nc; i++) cand = cand || cj == rl((int)ex, L0 + i);
+  return cand;
+}
+// stack time of a worker with more than one thread
+__device__ DGP_COLD double stack_time_cold(double occ, int nth) { return occ / (double)nth; }
+// exact stimuli (the oldest; scan mode reads processing_on): t has left its worker / x is placed
+__device__ DGP_COLD void exact_left_cold(int t) {
+  if (lane_id() == 0) c_dev.proc_on[t] = -1;
+  __threadfence_block();
+}
+__device__ DGP_COLD void exact_placed_cold(int x, int cb) {
+  if (lane_id() == 0) {
+    c_dev.proc_on[x] = cb;
+    c_dev.state[x] = S_PROCESSING;
+  }
+}
+// continue as the oldest stimulus: wait until every earlier one has retired
+__device__ DGP_COLD void wait_oldest_cold(long long r) {
+  SCtl& S = st_L().c;
+  while (vload(&S.seq_pos) != r) __builtin_amdgcn_s_sleep(1);
+  lds_fence();
+}
+
+#define LIKELY(x) __builtin_expect(!!(x), 1)
+#define UNLIKELY(x) __builtin_expect(!!(x), 0)
 
 // a stimulus whose effects stay on the workers it registered. Returns false (nothing
 // changed) when it needs every earlier stimulus retired first (needs scan mode).
@@ -2535,7 +2651,7 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
       const int slack = (WAITC && lane > 0 && (tv0 & T_CAND)) ? NXW / 2 : 0;
       bad = ctl == NL_OVF || (int)(ctl >> 8) + tot_new + slack > NLW - 1 + NXW;
     }
-    if (ballot(bad)) return false;
+    if (UNLIKELY(ballot(bad))) return false;
   }
   Out o;
   o.nrec = 0;
@@ -2567,8 +2683,8 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
   const int capw = P.cap[w];
   uint32_t nl = line_load<LW>(P, w);
   const unsigned long long wm = ballot(tl && cj == w);
-  if (!wm) {
-    serr(S, SERR_INV, 700000000 + (int)r);
+  if (UNLIKELY(!wm)) {
+    serr_cold(SERR_INV, 700000000 + (int)r);
     return true;
   }
   const int jw = __builtin_ctzll(wm);
@@ -2584,14 +2700,11 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
   // ------------------------------------------- completion: processing -> memory (:2366)
   int64_t dnet = 0;
   int64_t freed = 0;
-  if (needs_dec_all(E, TD, kt, w, nl, freed)) dnet = -freed;
-  else for (int i = 0; i < kt; i++) {  // _dec_needs_replica for the dependencies w needed
-    const int L_ = TD + i;
-    const int h = rl((int)E.y, L_);
-    if (h == w) continue;
-    const int d = rl((int)E.x, L_);
-    const int64_t nb = mk64(rlu(E.z, L_), rlu(E.w, L_));
-    dnet -= needs_dec(D, S, w, nl, d, nb, t);
+  if (LIKELY(needs_dec_all(E, TD, kt, w, nl, freed))) dnet = -freed;
+  else {  // _dec_needs_replica for the dependencies w needed, one at a time
+    const NeedsRes nr = needs_dec_each(E, TD, kt, w, nl, t);
+    nl = nr.nl;
+    dnet = -nr.v;
   }
   if (TR4 && lane == 0) TR(r, 24);
   const int npw = rl(np, jw) - 1;
@@ -2612,15 +2725,17 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
   // every lane's occupancy and stack time, kept current: only w (now) and each chosen
   // worker (after its commit) change during the stimulus
   double occj = occ_dict_r(dj, nbw, durv, D);
-  double stkj = nth1 ? occj : occj / (double)nth;
+  double stkj = LIKELY(nth1) ? occj : stack_time_cold(occj, nth);
   o.rec(D, K_COMPLETE, w, p, dnet, mkd(rlu(dlo(occj), jw), rlu(dhi(occj), jw)), npw, t, dobs);
   // add_replica (:3148), then the releases popped before the frontier (LIFO, :3309-3314)
   if (isw) nbj += (flags & F_SELFREL) ? 0 : nbt;
+  int64_t relj = 0;  // the released bytes this lane's worker held (candidate-only lanes take it after the wait)
   for (int i = 0; i < nrel; i++) {
     const int h = rl((int)E.x, RL0 + i);
     const int64_t nb = mk64(rlu(E.z, RL0 + i), rlu(E.w, RL0 + i));
-    if (tl && !wc && cj == h) nbj -= nb;
+    if (cj == h) relj += nb;
   }
+  if (tl && !wc) nbj -= relj;
   // a release-only holder (ws.nbytes of a released dependency; no frontier candidate) is final
   // now: written back and released before the frontier
   bool released = false;  // this lane's worker was written back and released early
@@ -2650,15 +2765,11 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
       net = P.netocc[cj];
       nbj = P.nbytes[cj];
     }
-    for (int i = 0; i < nrel; i++) {
-      const int h = rl((int)E.x, RL0 + i);
-      const int64_t nb = mk64(rlu(E.z, RL0 + i), rlu(E.w, RL0 + i));
-      if (wc && cj == h) nbj -= nb;
-    }
+    if (wc) nbj -= relj;
     if (wc) {
       nbw = net_bw_of(net, D);
       occj = occ_dict_r(dj, nbw, durv, D);
-      stkj = nth1 ? occj : occj / (double)nth;
+      stkj = LIKELY(nth1) ? occj : stack_time_cold(occj, nth);
     }
     if (!exact) {  // the candidates' needs tables, exactly now (the claim checked them with a margin)
       bool bad = false;
@@ -2666,9 +2777,8 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
         const uint32_t ctl = P.needs[(size_t)cj * NLW + NLW - 1];
         bad = ctl == NL_OVF || (int)(ctl >> 8) + tot_new > NLW - 1 + NXW;
       }
-      if (ballot(bad)) {  // rare: continue as the oldest stimulus (every earlier one retired)
-        while (vload(&S.seq_pos) != r) __builtin_amdgcn_s_sleep(1);
-        lds_fence();
+      if (UNLIKELY(ballot(bad))) {  // rare: continue as the oldest stimulus (every earlier one retired)
+        wait_oldest_cold(r);
         exact = true;
       }
     }
@@ -2685,16 +2795,15 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
     // candidates = the holders of x's dependencies (each a touched lane); comm_bytes (:3136)
     int64_t comm = 0;
     bool cand = false;
-    for (int i = 0; i < kx; i++) {
-      const int L2 = off + 1 + i;
-      const int hi = rl((int)E.y, L2);
-      const int64_t nbi = mk64(rlu(E.z, L2), rlu(E.w, L2));
+    const uint4 F = entries_from(E, off + 1);  // x's dependency entries in lanes 0..kx-1
+    each_dep(kx, [&](int i) {
+      const int hi = rl((int)F.y, i);
+      const int64_t nbi = mk64(rlu(F.z, i), rlu(F.w, i));
       if (cj == hi) cand = true;
       else comm += nbi;
-    }
-    if (hz & (1 << 16)) {  // restricted: the candidates PRE resolved (:8575-8586)
-      cand = false;
-      for (int i = 0; i < nc; i++) cand = cand || cj == rl((int)E.x, off + 1 + kx + i);
+    });
+    if (UNLIKELY(hz & (1 << 16))) {  // restricted: the candidates PRE resolved (:8575-8586)
+      cand = restr_cand_cold(E.x, off + 1 + kx, nc, cj);
     }
     cand = cand && tl;
     Key k;
@@ -2705,8 +2814,8 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
     phase(18);
     if (TR3 && lane == 0 && j == 0) TR(r, 13);
     const unsigned long long cm = ballot(cand);
-    if (!cm) {
-      serr(S, SERR_CAND, x);
+    if (UNLIKELY(!cm)) {
+      serr_cold(SERR_CAND, x);
       return true;
     }
     // key_less over the candidates, reading only what it compares: every candidate's start,
@@ -2763,20 +2872,17 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
     o.place(D, x, cb, best.comm, best.start, best.nb, ROUTE_NONROOTISH);
     uint32_t nlc = line_load<LW>(P, cb);
     if (TR4 && lane == 0 && j == 0) TR(r, 28);
-    if (exact) {  // scan mode reads processing_on of this stimulus' earlier placements
+    if (UNLIKELY(exact)) {  // scan mode reads processing_on of this stimulus' earlier placements
       // ... and of t, which left w above: a dependency t shares with x, placed on w, is not
       // needed by t any more (only an exact stimulus, the oldest, scans; the sequencer
       // writes this again at retirement)
-      if (lane == 0) D.proc_on[rl((int)E.x, 0)] = -1;
-      __threadfence_block();
+      exact_left_cold(t);
     }
     int64_t dn = 0;
-    if (!needs_inc_all(E, off + 1, kx, cb, nlc, dn)) for (int i = 0; i < kx; i++) {
-      const int L2 = off + 1 + i;
-      if (rl((int)E.y, L2) == cb) continue;
-      const int d = rl((int)E.x, L2);
-      const int64_t nb = mk64(rlu(E.z, L2), rlu(E.w, L2));
-      dn += needs_inc(D, S, cb, nlc, d, nb, x);
+    if (UNLIKELY(!needs_inc_all(F, 0, kx, cb, nlc, dn))) {  // _inc_needs_replica one at a time
+      const NeedsRes nr = needs_inc_each(E, off + 1, kx, cb, nlc, x);
+      nlc = nr.nl;
+      dn = nr.v;
     }
     if (TR4 && lane == 0 && j == 0) TR(r, 29);
     line_store<LW>(P, cb, nlc);
@@ -2789,14 +2895,13 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
     }
     if (TR4 && lane == 0 && j == 0) TR(r, 30);
     if (dn != 0) nbw = isb ? net_bw_of(net, D) : nbw;  // dn is uniform
-    if (ballot(!okp)) serr(S, SERR_PREFIX, x);
+    if (UNLIKELY(ballot(!okp))) serr_cold(SERR_PREFIX, x);
     if (TR4 && lane == 0 && j == 0) TR(r, 31);
-    if (exact && lane == 0) {  // scan mode reads them for this stimulus' later decisions (the
-      D.proc_on[x] = cb;       // sequencer writes them, and the group count, at retirement)
-      D.state[x] = S_PROCESSING;
-    }
+    // scan mode reads them for this stimulus' later decisions (the sequencer writes them, and
+    // the group count, at retirement)
+    if (UNLIKELY(exact)) exact_placed_cold(x, cb);
     occj = occ_dict_r(dj, nbw, durv, D);
-    stkj = nth1 ? occj : occj / (double)nth;
+    stkj = LIKELY(nth1) ? occj : stack_time_cold(occj, nth);
     o.rec(D, K_PLACE, cb, px, dn, mkd(rlu(dlo(occj), jb), rlu(dhi(occj), jb)), rl(np, jb), x, 0.0);
     off += 1 + kx + nc;
     phase(20);
@@ -2825,8 +2930,8 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
   int pops = 0;
   if (qmode != 0 && !D.sat_inf) {
     const int slots = capw - rl(np, jw);
-    if (slots > capw || o.npl + slots > PLC - 1) {
-      serr(S, SERR_INV, 600000000 + (int)r);
+    if (UNLIKELY(slots > capw || o.npl + slots > PLC - 1)) {
+      serr_cold(SERR_INV, 600000000 + (int)r);
       return true;
     }
     if (slots > 0) {
@@ -2845,9 +2950,9 @@ __device__ __attribute__((always_inline)) bool exe_local(const Dev& D, SLds& L, 
         okq = dict_add(dj, qp, +1);
         np += 1;
       }
-      if (ballot(!okq)) serr(S, SERR_PREFIX, -1);
+      if (UNLIKELY(ballot(!okq))) serr_cold(SERR_PREFIX, -1);
       occj = occ_dict_r(dj, nbw, durv, D);
-      stkj = nth1 ? occj : occj / (double)nth;
+      stkj = LIKELY(nth1) ? occj : stack_time_cold(occj, nth);
       o.rec(D, K_PLACE, w, qp, 0, mkd(rlu(dlo(occj), jw), rlu(dhi(occj), jw)), rl(np, jw), -1, 0.0);
     }
   }
