@@ -63,6 +63,7 @@ struct StealCtx {  // WorkStealing arrays of the last dgp_steal_load (one arena)
   bool loaded = false;
   // dgp_steal_order for the next load: the tasks' (priority, arrival) keys (host)
   std::vector<int64_t> order_prio, order_arr;
+  bool order_pending = false;
 };
 
 struct dgp_engine {
@@ -3685,10 +3686,20 @@ int dgp_steal_load(dgp_engine* e, int32_t W, const int32_t* nthreads, const doub
                    const int64_t* d_nbytes, const int64_t* d_get_nbytes, const int64_t* h_ptr, const int32_t* h_idx,
                    const int64_t* r_ptr, const int32_t* r_idx, const uint8_t* r_flags, const int8_t* level_in,
                    const double* ifo_in, const int32_t* ift_in, int64_t* n_stealable) {
+  // dgp_steal_order's keys are for this call alone, however it ends
+  std::vector<int64_t> order_prio, order_arr;
+  bool order_pending = false;
+  if (e) {
+    order_prio.swap(e->steal.order_prio);
+    order_arr.swap(e->steal.order_arr);
+    std::swap(order_pending, e->steal.order_pending);
+  }
   if (int rc_ = resident_stop(e)) return rc_;
   namespace S = dgp::steal;
   if (!e) return DGP_E_ARG;
   e->steal.loaded = false;
+  if (order_pending && (int64_t)order_prio.size() != T)
+    return fail(e, DGP_E_ARG, "dgp_steal_load: dgp_steal_order gave keys for another n_tasks");
   if (W <= 0 || T < 0 || n_data < 0 || bandwidth <= 0 || total_nthreads <= 0 || !nthreads || !occ || !nproc ||
       !wnbytes || !idle || !sat || !n_stealable || (T && (!victim || !duration || !fast || !dep_ptr)) ||
       (n_data && (!d_nbytes || !d_get_nbytes || !h_ptr)))
@@ -3755,7 +3766,7 @@ int dgp_steal_load(dgp_engine* e, int32_t W, const int32_t* nthreads, const doub
   chk(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_a, (uint64_t*)nullptr, (uint64_t*)nullptr, (int32_t*)nullptr,
                                          (int32_t*)nullptr, W, 0, 64, s));
   // dgp_steal_order: the tasks' (priority, arrival) order, two stable 64-bit sorts
-  const bool ordered = (int64_t)e->steal.order_prio.size() == T && T > 0;
+  const bool ordered = order_pending && T > 0;
   size_t tmp_ord = 0;
   if (ordered)
     chk(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_ord, (uint64_t*)nullptr, (uint64_t*)nullptr, (int32_t*)nullptr,
@@ -3856,8 +3867,8 @@ int dgp_steal_load(dgp_engine* e, int32_t W, const int32_t* nthreads, const doub
         // sort below then keeps that order inside each bin. Keys go through the sign bit
         // flipped (int64 order as uint64).
         const unsigned gt = (unsigned)((T + 255) / 256);
-        chk(hipMemcpyAsync(d_ok1, C.order_prio.data(), T * 8, hipMemcpyHostToDevice, s));
-        chk(hipMemcpyAsync(d_ok2, C.order_arr.data(), T * 8, hipMemcpyHostToDevice, s));
+        chk(hipMemcpyAsync(d_ok1, order_prio.data(), T * 8, hipMemcpyHostToDevice, s));
+        chk(hipMemcpyAsync(d_ok2, order_arr.data(), T * 8, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(S::k_flip_sign, dim3(gt), dim3(256), 0, s, d_ok1, T);
         hipLaunchKernelGGL(S::k_flip_sign, dim3(gt), dim3(256), 0, s, d_ok2, T);
         hipLaunchKernelGGL(dgp::k_iota32, dim3(gt), dim3(256), 0, s, d_perm1, (int)T);
@@ -3890,7 +3901,8 @@ int dgp_steal_load(dgp_engine* e, int32_t W, const int32_t* nthreads, const doub
     if (!rc) chk(hipMemcpyAsync(&nst, P.bin_ptr + NK - 1, 4, hipMemcpyDeviceToHost, s));
   } else {
     chk(hipMemsetAsync(P.bin_ptr, 0, NK * 4, s));
-    chk(hipMemsetAsync(P.n_runs, 0, 4, s));  // no thief runs are read without tasks
+    chk(hipMemsetAsync(P.n_runs, 0, 4, s));  // no thief runs are read without tasks,
+    chk(hipMemsetAsync(P.run_start, 0, 4, s));  // but k_balance reads where the last run ends
   }
   chk(hipStreamSynchronize(s));
   if (rc) return rc;
@@ -3898,8 +3910,6 @@ int dgp_steal_load(dgp_engine* e, int32_t W, const int32_t* nthreads, const doub
   if (nst < 0 || nst > T) return fail(e, DGP_E_STATE, "dgp_steal_load: bin scan out of range");
   C.n_stealable = nst;
   C.loaded = true;
-  C.order_prio.clear();
-  C.order_arr.clear();
   *n_stealable = nst;
   return 0;
 }
@@ -3909,6 +3919,7 @@ int dgp_steal_order(dgp_engine* e, int64_t n_tasks, const int64_t* priority, con
   if (n_tasks < 0 || (n_tasks && (!priority || !arrival))) return fail(e, DGP_E_ARG, "dgp_steal_order: bad arrays");
   e->steal.order_prio.assign(priority, priority + n_tasks);
   e->steal.order_arr.assign(arrival, arrival + n_tasks);
+  e->steal.order_pending = true;
   return 0;
 }
 

@@ -805,7 +805,10 @@ int dgp_steal_balance(dgp_engine* e, int32_t n_workers, const int32_t* nthreads,
 /* dgp_steal_order: the next dgp_steal_load / dgp_steal_balance takes its tasks in ascending
  * (priority, arrival) instead of their input order (the order the bins are walked in,
  * stealing.py:441-461 with the canonical tie-break), sorted on the device; n_tasks must be
- * that call's n_tasks. The plugin keeps its task rows in arrival slots (no host sort per
+ * that call's n_tasks: a load with another n_tasks is refused (DGP_E_ARG). The keys are for
+ * that one dgp_steal_load (dgp_steal_balance begins with one), which drops them however it
+ * ends (refused, failed or done): a load after it without a dgp_steal_order of its own walks
+ * in input order. The plugin keeps its task rows in arrival slots (no host sort per
  * balance() call). Outputs still index the tasks in input order. (ABI 18) */
 int dgp_steal_order(dgp_engine* e, int64_t n_tasks, const int64_t* priority, const int64_t* arrival);
 /* dgp_steal_balance in phases, for a balance() sharded over ranks (one engine per GPU):
